@@ -14,6 +14,11 @@ data parallelism (one sample per GPU, gradient all-reduce overlapped with backwa
 headline IS data parallelism (the reference's partitioning has no 2-GPU split worth running on xGMI: default_parallelism).
 ``--parallelism dp|hHwW`` picks the headline explicitly.
 
+A plain run sets up, warms up, times the K steps and prints the headline.  ``--full`` adds everything else the line can
+carry: per-kernel table and roofline, the step with exact fp32 spectral arithmetic, forward SHT bandwidth, CPU baseline,
+in-run parity against the oracle and, at N > 1, the exchange volume and the data-parallel ``secondary``.
+``--dump-outputs DIR`` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``).
+
 Rank 0 prints ONE JSON line (see DESIGN.md §7 for every field).
 """
 import argparse
@@ -311,6 +316,37 @@ def train_step(model, opt, inp, tar, loss_fn, amp, sharded_clip):
     else:
         opt.step(max_grad_norm=32.0)      # global-norm clipping folded into the AdamW pass
     return loss
+
+
+DUMP_SEED = 20261016
+DUMP_MAX_ELEMENTS = 1 << 22          # per file: 16 MB of float32 for the parameters, as much for the gradients
+
+
+def _dump_sample(tensors, gen):
+    """every tensor flattened (complex through its real view), in order; a tensor larger than its share of
+    DUMP_MAX_ELEMENTS contributes that many entries at seeded positions (the same positions in every run)"""
+    cap = max(1, DUMP_MAX_ELEMENTS // max(1, len(tensors)))
+    parts = []
+    for t in tensors:
+        flat = (torch.view_as_real(t) if t.is_complex() else t).detach().reshape(-1)
+        if flat.numel() > cap:
+            idx = torch.randint(flat.numel(), (cap,), generator=gen).sort().values
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy() if parts else torch.zeros(0).numpy()
+
+
+def dump_outputs(path, loss, model):
+    """--dump-outputs: what the last timed train step handed back, for comparing two builds output for output — its loss,
+    and every parameter after the AdamW update with its gradient (named_parameters order; a parameter without a gradient
+    contributes zeros)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    params = [p for _, p in model.named_parameters()]
+    grads = [p.grad if p.grad is not None else torch.zeros_like(p) for p in params]
+    np.save(os.path.join(path, "loss.npy"), np.asarray([float(loss.detach().float().reshape(-1)[0])], dtype=np.float64))
+    np.save(os.path.join(path, "params.npy"), _dump_sample(params, torch.Generator().manual_seed(DUMP_SEED)))
+    np.save(os.path.join(path, "grads.npy"), _dump_sample(grads, torch.Generator().manual_seed(DUMP_SEED)))
 
 
 def sht_bandwidth(device, reps=5):
@@ -860,9 +896,9 @@ def run_worker(args):
     model = build_model(args.config, device, seed=333)            # same seed on every rank -> same init
     opt = make_optimizer(model, lr=cfg.get("lr", 1e-3))
     probe = None
-    if world == 1 and not args.no_cpu_baseline and args.config == "sfno_sc3_layers8_edim384":
+    if world == 1 and args.full and not args.no_cpu_baseline and args.config == "sfno_sc3_layers8_edim384":
         probe = ParityProbe(model, cfg, device)                    # before the first update: the weights the oracle will load
-    elif world == 1 and not args.no_cpu_baseline and fcn3:
+    elif world == 1 and args.full and not args.no_cpu_baseline and fcn3:
         try:
             probe = Fcn3ParityProbe(model, cfg, device)            # block level (the whole network is minutes of host time)
         except Exception as e:                                     # the probe must never cost the measurement
@@ -905,9 +941,9 @@ def run_worker(args):
     spectral_train = amp and args.spectral == "train"
     torch.backends.cuda.matmul.allow_tf32 = bool(spectral_train)
 
-    # Per-kernel HIP events cost ~1.2 ms/step (2 events x ~300 C-ABI launches).  The LAST warm-up step is
-    # profiled in full: it yields the per-kernel table and names the dominant HIP kernel; inside the timed region
-    # only that kernel carries events (its roofline numbers therefore come from the timed steps).  With
+    # Per-kernel HIP events cost ~1.2 ms/step (2 events x ~300 C-ABI launches), so only --full records them.  The LAST
+    # warm-up step is profiled in full: it yields the per-kernel table and names the dominant HIP kernel; inside the timed
+    # region only that kernel carries events (its roofline numbers therefore come from the timed steps).  With
     # --warmup 0 every launch of the timed region is instrumented instead.
     # Python's cyclic collector is paused for the warm-up and the timed loop: a generation-2 collection over the
     # autograd graphs stalls the launching thread for ~100 ms (measured with tools/step_times.py: one step of 154 ms
@@ -917,7 +953,7 @@ def run_worker(args):
     gc.disable()
     warm_prof, dom_family, dom_members = {}, None, []
     for i in range(args.warmup):
-        last = i == args.warmup - 1
+        last = args.full and i == args.warmup - 1
         if last:
             torch.cuda.synchronize()
             ops.PROFILER.reset()
@@ -985,7 +1021,7 @@ def run_worker(args):
                 print(f"[bench] {graph_note}", file=sys.stderr, flush=True)
 
     ops.PROFILER.reset()
-    ops.PROFILER.enabled = graph is None
+    ops.PROFILER.enabled = args.full and graph is None
     ops.PROFILER.only = set(dom_members) if dom_members else None      # HIP events on the dominant kernel only (see above)
     thd.COMM_STATS.clear()                                             # all-to-all accounting of the timed steps (N > 1)
     if world > 1:
@@ -1006,10 +1042,12 @@ def run_worker(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     ops.PROFILER.enabled = False
+    if args.dump_outputs and rank == 0:          # before anything below runs another step on the same weights
+        dump_outputs(args.dump_outputs, loss, model)
     comm_stats = {f"{k[0]}_group_of_{k[1]}": dict(MB_sent=round(v["bytes_sent"] / args.steps / 1e6, 2), all_to_alls=v["all_to_alls"] / args.steps)
                   for k, v in sorted(thd.COMM_STATS.items())}
     event_steps = args.steps
-    if graph is not None:
+    if graph is not None and args.full:
         # launch durations of the dominant kernel: HIP events cannot bracket a node inside a replayed graph, so the same
         # launches are timed in eager steps right after the timed region (same process, same tensors, same shapes)
         event_steps = 3
@@ -1030,7 +1068,7 @@ def run_worker(args):
     # the same step with the spectral GEMMs in fp32-class arithmetic (three limbs): captured and timed the same way, reported
     # beside the headline so that both settings of the switch are on record from ONE run
     exact = None
-    if spectral_train and world == 1 and graph is not None and not args.no_exact:
+    if args.full and spectral_train and world == 1 and graph is not None and not args.no_exact:
         try:
             torch.backends.cuda.matmul.allow_tf32 = False
             for _ in range(2):
@@ -1059,24 +1097,6 @@ def run_worker(args):
 
     out = None
     if rank == 0:
-        prof = ops.PROFILER.summary()           # timed region: the dominant kernel (or everything with --warmup 0)
-        # dominant HIP kernel = the kernel family with the largest accumulated time among our launches (what the
-        # rocprofv3 --stats table of the same command shows on top); its numbers come from the timed steps
-        if not (dom_family and any(m in prof for m in dom_members)):
-            dom_family, dom_members = dominant_family(prof)
-        kernels = kernel_table(warm_prof, prof, event_steps)
-        pmc = load_pmc_traffic(fcn3) if (args.config in ("sfno_sc3_layers8_edim384", "fcn3_sc2_edim45_layers10") and msize == 1) else {}
-        roofline = roofline_of(dom_family, dom_members, prof, ops.gemm_mode(), pmc.get(dom_family)) if dom_family else None
-        # the runners-up, from the fully profiled warm-up step (one launch set, not an average over the timed steps)
-        others = []
-        if warm_prof:
-            fams = {}
-            for k in warm_prof:
-                fams.setdefault(kernel_family(k), []).append(k)
-            rank_f = sorted(fams, key=lambda f: -sum(warm_prof[k]["ms_total"] for k in fams[f]))
-            for f in [f for f in rank_f if f != dom_family][:4]:
-                others.append(roofline_of(f, sorted(fams[f]), warm_prof, ops.gemm_mode(), pmc.get(f)))
-        hip_ms = sum(v["ms_per_step"] for v in kernels.values())
         out = {
             "metric": (f"FourCastNet3 train samples/sec at {H}x{W}x{cfg['out_chans']}ch" if fcn3 else
                        f"SFNO train samples/sec at {H}x{W}x{cfg['inp_chans']}ch"),
@@ -1104,22 +1124,38 @@ def run_worker(args):
                        "collectives": (dist.get_backend() if world > 1 else None),
                        "launch": ("hipGraph replay of the captured step" if graph is not None else "eager"),
                        "channel_gemm": "hip (csrc/conv1x1.hip)"},
-            "exact_fp32_spectral": exact,
-            "roofline": roofline,
-            "roofline_runners_up": others,
             "peak_hbm_GB": round(torch.cuda.max_memory_allocated() / 1e9, 2),
-            "hip_kernels": kernels,
-            "hip_kernel_ms_per_step": round(hip_ms, 2),
             "final_loss": final_loss,
         }
+        if graph_note:
+            out["note"] = graph_note
+    if rank == 0 and args.full:
+        prof = ops.PROFILER.summary()           # timed region: the dominant kernel (or everything with --warmup 0)
+        # dominant HIP kernel = the kernel family with the largest accumulated time among our launches (what the
+        # rocprofv3 --stats table of the same command shows on top); its numbers come from the timed steps
+        if not (dom_family and any(m in prof for m in dom_members)):
+            dom_family, dom_members = dominant_family(prof)
+        kernels = kernel_table(warm_prof, prof, event_steps)
+        pmc = load_pmc_traffic(fcn3) if (args.config in ("sfno_sc3_layers8_edim384", "fcn3_sc2_edim45_layers10") and msize == 1) else {}
+        roofline = roofline_of(dom_family, dom_members, prof, ops.gemm_mode(), pmc.get(dom_family)) if dom_family else None
+        # the runners-up, from the fully profiled warm-up step (one launch set, not an average over the timed steps)
+        others = []
+        if warm_prof:
+            fams = {}
+            for k in warm_prof:
+                fams.setdefault(kernel_family(k), []).append(k)
+            rank_f = sorted(fams, key=lambda f: -sum(warm_prof[k]["ms_total"] for k in fams[f]))
+            for f in [f for f in rank_f if f != dom_family][:4]:
+                others.append(roofline_of(f, sorted(fams[f]), warm_prof, ops.gemm_mode(), pmc.get(f)))
+        hip_ms = sum(v["ms_per_step"] for v in kernels.values())
+        out.update({"exact_fp32_spectral": exact, "roofline": roofline, "roofline_runners_up": others, "hip_kernels": kernels,
+                    "hip_kernel_ms_per_step": round(hip_ms, 2)})
         if msize > 1:
             # what this rank (rank 0) puts on the links per step in the distributed transforms, by size of the process group the
             # all-to-all runs over (h, w or h x w) — to be read against SURVEY.md §8(e)'s 9.4 ms/step communication budget
             out["exchange_per_step_rank0"] = dict(comm_stats, total_MB_sent=round(sum(v["MB_sent"] for v in comm_stats.values()), 2),
                                                   schedule=("fused (one h x w all-to-all between FFT and Legendre transform)"
                                                             if os.environ.get("MAKANI_AMD_DIST_FUSED", "1") == "1" else "transpose by transpose"))
-        if graph_note:
-            out["note"] = graph_note
         if graph is not None and roofline:
             roofline["timing"] = (f"HIP events around the launches in {event_steps} eager steps run right after the timed region "
                                   "(the timed steps are hipGraph replays, whose nodes cannot carry events)")
@@ -1193,10 +1229,14 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _worker_cmd(args, parallelism):
+def _worker_cmd(args, parallelism, dump=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--gpus", str(args.gpus), "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--config", args.config, "--parallelism", parallelism, "--no-sht-metric",
            "--no-cpu-baseline", "--multistep-count", str(args.multistep_count), "--graph", args.graph, "--spectral", args.spectral]
+    if args.full:
+        cmd.append("--full")
+    if dump and args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.fp32:
         cmd.append("--fp32")
     if args.zero:
@@ -1206,7 +1246,7 @@ def _worker_cmd(args, parallelism):
     return cmd
 
 
-def _run_phase(args, parallelism, ranks, world, port, timeout_s):
+def _run_phase(args, parallelism, ranks, world, port, timeout_s, dump=False):
     """start one worker process per rank in ``ranks`` (all N when this script is the launcher, only our own when the
     driver's torch.distributed.run started one copy of this script per GPU), wait, return rank 0's JSON (or None) and
     an error string"""
@@ -1228,7 +1268,7 @@ def _run_phase(args, parallelism, ranks, world, port, timeout_s):
             per = max(1, 256 // world)
             env["HSA_CU_MASK"] = f"0:{r * per}-{(r + 1) * per - 1}"
         keep_out = (r == 0)
-        procs.append((r, subprocess.Popen(_worker_cmd(args, parallelism), env=env, stdout=subprocess.PIPE if keep_out else subprocess.DEVNULL,
+        procs.append((r, subprocess.Popen(_worker_cmd(args, parallelism, dump), env=env, stdout=subprocess.PIPE if keep_out else subprocess.DEVNULL,
                                           stderr=None, text=True)))
     result, err = None, None
     deadline = time.time() + timeout_s
@@ -1252,8 +1292,8 @@ def _run_phase(args, parallelism, ranks, world, port, timeout_s):
 
 
 def launch(args):
-    """N > 1.  Phase 1: the headline parallelism; phase 2: plain data parallelism as ``secondary`` (skipped when the
-    headline already is dp or with --no-secondary).  Each phase is its own set of worker processes with its own
+    """N > 1.  Phase 1: the headline parallelism; phase 2 (--full only): plain data parallelism as ``secondary`` (skipped when
+    the headline already is dp or with --no-secondary).  Each phase is its own set of worker processes with its own
     rendezvous port, so a failure in one (say, an RCCL all-to-all problem) cannot take the other measurement with it."""
     under_torchrun = int(os.environ.get("WORLD_SIZE", "1")) > 1
     world = int(os.environ["WORLD_SIZE"]) if under_torchrun else args.gpus
@@ -1261,7 +1301,7 @@ def launch(args):
     ranks = [rank] if under_torchrun else list(range(world))
     base_port = int(os.environ.get("MASTER_PORT", "0")) if under_torchrun else 0
     head = args.parallelism if args.parallelism != "auto" else default_parallelism(world, args.config)
-    phases = [head] + (["dp"] if (head != "dp" and not args.no_secondary) else [])
+    phases = [head] + (["dp"] if (head != "dp" and args.full and not args.no_secondary) else [])
     timeout_s = int(os.environ.get("MAKANI_AMD_BENCH_PHASE_TIMEOUT", "360"))
     results, errors = {}, {}
     if under_torchrun:                         # the copies of this script agree on each phase's outcome over a host-side group
@@ -1284,7 +1324,7 @@ def launch(args):
             os.environ.update(env_over)
             # the first attempt (captured step) gets a shorter leash: a capture that hangs must not eat the time of the eager retry
             first_graph = (not env_over) and eager
-            res, err = _run_phase(args, par, ranks, world, port, min(timeout_s, 200) if first_graph else timeout_s)
+            res, err = _run_phase(args, par, ranks, world, port, min(timeout_s, 200) if first_graph else timeout_s, dump=par == head)
             for k in env_over:
                 os.environ.pop(k, None)
             if env_over and res is not None and not err:
@@ -1356,6 +1396,13 @@ def main():
                          "1 = the headline single-step metric")
     ap.add_argument("--multistep-checkpoint", action="store_true",
                     help="recompute each rollout step's network call in backward (makani's --multistep_checkpoint)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline: per-kernel table and roofline (with live counter "
+                         "passes), the step with exact fp32 spectral arithmetic, forward SHT bandwidth, CPU baseline and in-run "
+                         "parity against the oracle; N > 1: exchange volume and the data-parallel secondary phase")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, gradients and updated "
+                         "parameters; large tensors as a fixed seeded sample) as DIR/<name>.npy")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-mode", default="fwd", help=argparse.SUPPRESS)

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "sfno_debug", "--steps", "2", "--warmup", "1",
-                          "--no-sht-metric"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--no-sht-metric", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -28,6 +28,66 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     for k in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert k in r, k
     assert r["bound"] in ("hbm", "mfma") and abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-3
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """without --full the line carries the headline only (none of the figures that take extra work), and --dump-outputs writes
+    the last timed step's loss, parameters and gradients as float .npy files within 64 MB"""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "sfno_debug", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "samples/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    for k in ("roofline", "hip_kernels", "exact_fp32_spectral", "cpu_baseline", "parity_rel_l2", "fwd_sht"):
+        assert k not in d, k
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["grads.npy", "loss.npy", "params.npy"]
+    arrays = {f: np.load(tmp_path / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["params.npy"].shape == arrays["grads.npy"].shape and np.abs(arrays["grads.npy"]).max() > 0
+    assert arrays["loss.npy"][0] == d["final_loss"]
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample(tmp_path):
+    """bench.dump_outputs on a CPU model: small tensors whole, a tensor above its share of the budget as a sample at seeded
+    positions (the same in every run), parameters and gradients aligned entry for entry"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def run(d):
+        torch.manual_seed(0)
+        lin = torch.nn.Linear(8, 4)
+        big = torch.nn.Parameter(torch.view_as_complex(torch.arange(2.0 * bench.DUMP_MAX_ELEMENTS).reshape(-1, 2)))
+        unused = torch.nn.Parameter(torch.ones(3))
+        m = torch.nn.Module()
+        m.lin, m.big, m.unused = lin, big, unused
+        loss = lin(torch.rand(5, 8)).square().mean() + big.real.sum()
+        loss.backward()
+        bench.dump_outputs(str(d), loss, m)
+        return {f: np.load(d / f"{f}.npy") for f in ("loss", "params", "grads")}, loss, lin
+
+    a, loss, lin = run(tmp_path / "a")
+    b, _, _ = run(tmp_path / "b")
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert a["loss"][0] == float(loss)
+    cap = bench.DUMP_MAX_ELEMENTS // 4                 # named_parameters order: big, unused, lin.weight, lin.bias
+    sample = a["params"][:cap]                         # the real view of ``big`` holds its own flat positions
+    assert len(sample) == cap and np.all(np.diff(sample) >= 0) and sample.max() < 2 * bench.DUMP_MAX_ELEMENTS
+    assert np.array_equal(a["grads"][:cap], (sample % 2 == 0).astype(np.float32))      # d loss / d re = 1, d / d im = 0
+    assert np.array_equal(a["params"][cap:cap + 3], np.ones(3, np.float32)) and np.array_equal(a["grads"][cap:cap + 3], np.zeros(3, np.float32))
+    small = torch.cat([lin.weight.detach().reshape(-1), lin.bias.detach()]).numpy()
+    assert np.array_equal(a["params"][cap + 3:], small)
+    assert np.array_equal(a["grads"][cap + 3:], torch.cat([lin.weight.grad.reshape(-1), lin.bias.grad]).numpy())
+    assert len(a["params"]) <= bench.DUMP_MAX_ELEMENTS and sum(x.nbytes for x in a.values()) <= 64 << 20
 
 
 @pytest.mark.gpu
@@ -51,7 +111,7 @@ def test_bench_launches_its_own_ranks_headline_split_and_secondary_dp():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "sfno_debug", "--steps", "2",
-                          "--warmup", "1", "--parallelism", "h2w1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--warmup", "1", "--parallelism", "h2w1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -73,7 +133,7 @@ def test_bench_eight_ranks_h4w2_line_shape():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--config", "sfno_debug_seg", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=1700, cwd=ROOT, env=env)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=1700, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -171,7 +231,7 @@ def test_roofline_report_on_a_synthetic_profile():
 def test_bench_fcn3_workload_runs_the_ensemble_recipe():
     """--config fcn3_debug: the FourCastNet3 workload of BASELINE configs[3] on a small grid — ensemble members in the model's
     batch, fair CRPS + 0.1 x spectral CRPS, clip + FusedAdamW; the roofline object names a kernel of the step"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "fcn3_debug", "--steps", "2", "--warmup", "1"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "fcn3_debug", "--steps", "2", "--warmup", "1", "--full"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
