@@ -18,13 +18,8 @@
 #include <type_traits>
 
 #include "common.h"
+#include "conv1x1_plan.h"
 
-#ifndef MK_ASTAT_EPI_DRAIN
-#define MK_ASTAT_EPI_DRAIN 0
-#endif
-#ifndef MK_A2_PRIO              // conv_nn_astat2_kernel: s_setprio 1 around the multiplication phases (A/B knob)
-#define MK_A2_PRIO 1
-#endif
 // timing diagnostic of the weight-stationary kernel (tools/astat_diag.py; build with -DMK_ASTAT_DIAG=1): s_memtime stamps at the
 // segment boundaries of every pixel tile, summed per wave into g_astat_diag:
 // [0 wait for the chunk + barrier, 1 fragment reads + MFMAs, 2 next chunk's DMA issue, 3 epilogue: convert + stage, 4 barrier,
@@ -877,11 +872,6 @@ __global__ __launch_bounds__(256, (KS < 24 && !EPI_LOADS) ? 2 : 1) void conv_nn_
                 // the LOOK - 1 younger chunks, the stores of the nfull tile ends in between and the operand images of the tile
                 // starts strictly in between (nfull of them, one fewer when this step is itself a tile start: its images are
                 // requested behind this wait).  The first tiles have fewer epilogues behind them: drained.
-#if MK_ASTAT_EPI_DRAIN          // the round-3 behaviour, kept for the same-box A/B (tools/ab_fast.sh conv1x1 drain:-DMK_ASTAT_EPI_DRAIN=1)
-                if (kc == 0) wait_vmcnt<0>();
-                if (true) {
-                } else
-#endif
                 if (ts < NEPI_MAX) {
                     wait_vmcnt<0>();
                 } else if (kc == 0) {
@@ -1215,9 +1205,7 @@ __global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const ConvNN p, int
         };
         bf16x8 xf[2][2];
         frags(xf[0], 0);
-#if MK_A2_PRIO
         __builtin_amdgcn_s_setprio(1);
-#endif
 #pragma unroll
         for (int sub = 0; sub < 2 * K4; ++sub) {
             if (sub + 1 < 2 * K4) frags(xf[(sub + 1) & 1], sub + 1);
@@ -1229,9 +1217,7 @@ __global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const ConvNN p, int
                     acc[2 * hp + j][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf[sub & 1][j], wf[ct][kc * K4 + k4], acc[2 * hp + j][ct], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-#if MK_A2_PRIO
         __builtin_amdgcn_s_setprio(0);
-#endif
     };
     auto stage = [&]() __attribute__((always_inline)) {                                // 48 rows of this wave x 64 pixels -> the group's staging image (bf16)
         const int ln = lane_here();
@@ -1826,6 +1812,11 @@ extern "C" int mk_astat_diag_read(unsigned long long* out, int reset) {
 }
 #endif
 
+static int env_int(const char* name) {       // -1: unset
+    const char* e = getenv(name);
+    return e ? atoi(e) : -1;
+}
+
 extern "C" int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, const float* bias, const void* R,
                              const void* G, int M, int K, int lda, int B, long long N, int act, void* stream) {
     MK_REQUIRE(A && X && Y, "conv1x1_nn: null pointer");
@@ -1833,113 +1824,78 @@ extern "C" int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, 
     MK_REQUIRE((lda % 8) == 0 && lda >= K, "conv1x1_nn: lda=%d must be a multiple of 8 and >= K=%d", lda, K);
     MK_REQUIRE((N % 8) == 0, "conv1x1_nn: pixel count %lld must be a multiple of 8", N);
     MK_REQUIRE((((uintptr_t)A | (uintptr_t)X) & 15) == 0, "conv1x1_nn: operands must be 16-byte aligned");
-    // streaming stores for outputs that fit the memory-side cache (256 MB) — see mk_st16.  MAKANI_AMD_CONV_NT=0 / 1: never / always (2: by the sum of both outputs)
-    static const int nt_env = [] { const char* e = getenv("MAKANI_AMD_CONV_NT"); return e ? atoi(e) : -1; }();
+    // MAKANI_AMD_CONV_NT (0 / 1: streaming output stores never / always) and MAKANI_AMD_ASTAT2 (see conv_nn_plan): unset = -1
+    static const int nt_env = env_int("MAKANI_AMD_CONV_NT"), astat2_env = env_int("MAKANI_AMD_ASTAT2");
+    // streaming stores for outputs that fit the memory-side cache (256 MB) — see mk_st16
     const long long out_bytes = (long long)B * M * N * 2;          // per output tensor (with the pre-activation there are two)
-    const int nt = nt_env >= 0 ? (nt_env == 1 || (nt_env == 2 && out_bytes * ((act && Ypre) ? 2 : 1) <= (256ll << 20))) : (out_bytes <= (256ll << 20));
+    const int nt = nt_env == 0 ? 0 : (nt_env == 1 ? 1 : out_bytes <= (256ll << 20));
     ConvNN p{(const u16*)A, (const u16*)X, (u16*)Y, (u16*)Ypre, bias, (const u16*)R, (const u16*)G, M, K, lda, B, N, act, nt};
-    static const bool force_tile = [] { const char* e = getenv("MAKANI_AMD_CONV_NN"); return e && e[0] == 't'; }();
-    static const bool no_astat = [] { const char* e = getenv("MAKANI_AMD_CONV_NN"); return e && e[0] == 'r'; }();   // "ring": no weight-stationary kernel
-    if (!force_tile && !no_astat && lda == 80 && K > 64 && K <= 80 && M >= 256 && (long long)M * N * 2 < (1ll << 31) &&
-        (long long)K * N * 2 < (1ll << 32) && N >= 64 && !(R && G) && !((R || G) && act && Ypre)) {
-        // the 73-channel edges (K padded to lda = 80): the weight-stationary kernel with 5 k16-steps and one 96-row chunk per tile
-        const bool epi_loads = R || G;
-        const int slabs = (M + 383) / 384;
-        const long long tn = (N + 63) / 64;
-        const int wgs = epi_loads ? 256 : 512;                     // two workgroups per CU without the epilogue operand images
-        const long long streams = tn < wgs / slabs ? tn : wgs / slabs;
-        const dim3 grid((unsigned)(streams * slabs), (unsigned)B), blk(256);
-        const bool pre = act && Ypre;
-        hipStream_t s = (hipStream_t)stream;
-        if (epi_loads) hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, false, true, 5>), grid, blk, 0, s, p, slabs, tn);
-        else if (pre) hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, true, false, 5>), grid, blk, 0, s, p, slabs, tn);
-        else hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, false, false, 5>), grid, blk, 0, s, p, slabs, tn);
-        return mk_check_launch("mk_conv1x1_nn");
+    hipStream_t s = (hipStream_t)stream;
+    const bool pre = act && Ypre, epi_loads = R || G;
+    // the weight-stationary kernels: 384-channel slabs (4 waves x 3 row tiles; 256-row slabs measured slower), 64-pixel tiles, a
+    // persistent grid of `wgs` workgroups
+    const int slabs = (M + 383) / 384;
+    const long long tn64 = (N + 63) / 64;
+    auto stationary_grid = [&](int wgs) {
+        const long long streams = tn64 < wgs / slabs ? tn64 : wgs / slabs;
+        return dim3((unsigned)(streams * slabs), (unsigned)B);
+    };
+    switch (conv_nn_plan(M, K, lda, B, N, pre, R != nullptr, G != nullptr, astat2_env)) {
+    case ConvNnKernel::astat73: {
+        const dim3 grid = stationary_grid(epi_loads ? 256 : 512), blk(256);      // two workgroups per CU without the epilogue operand images
+        if (epi_loads) hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, false, true, 5>), grid, blk, 0, s, p, slabs, tn64);
+        else if (pre) hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, true, false, 5>), grid, blk, 0, s, p, slabs, tn64);
+        else hipLaunchKernelGGL((conv_nn_astat_kernel<3, 96, false, false, 5>), grid, blk, 0, s, p, slabs, tn64);
+        break;
     }
-    // MAKANI_AMD_ASTAT2: 0 = never, unset / 1 = every K = 384 launch, 3 = round 4's rule (profiles/r04_ab_astat2.txt: plain -7 %, gelu'
-    // -14 ... -22 %, skip operand -10 ... -21 %; bias + GELU + pre-activation — two output streams, then bound by its stores —
-    // +0 ... 2 %, so that variant stayed on the one-group kernel).  Round 6, with the streaming stores and the one-exponential GELU
-    // (gpurun_out/r07y, same box): that variant now runs 10 - 11 % faster on the two-group kernel at 115 200 pixels (0.134 -> 0.119,
-    // 0.072 -> 0.065 ms), 4 % at 384 <- 384 / 1 038 240 pixels, equal at 768 <- 384 / 1 038 240: every K = 384 launch takes it
-    static const int astat2 = [] { const char* e = getenv("MAKANI_AMD_ASTAT2"); return e ? atoi(e) : 2; }();
-    // shard-sized grids (one rank of h4 w2 holds 14 400 ... 32 400 pixels of the internal grid): for 384 <- 384 the ring kernel beats the
-    // weight-stationary ones by 10 - 25 % there (plain 14.5 / 16.3 us against 18.8 / 21.8, + skip operand 16.3 / 18.4 against 18.2 / 24.3:
-    // profiles/r05_ab_conv_shard_kernel_choice.txt); from 115 200 pixels on the stationary kernels win everywhere
-    const bool small_ring = K == 384 && M == 384 && (long long)B * N <= 32768 && !(act && Ypre) && astat2 != 1;
-    if (astat2 && (astat2 != 3 || !(act && Ypre && !(R || G))) && !small_ring && !force_tile && !no_astat && K == 384 && M >= 256 &&
-        (long long)M * N * 2 < (1ll << 31) && N >= 64 && !(R && G)) {
-        // two wave groups, one multiplying while the other runs its epilogue (conv_nn_astat2_kernel): 384-channel slabs
-        const bool epi_loads = R || G;
-        const int slabs = (M + 383) / 384;
-        const long long tn = (N + 63) / 64;
-        const long long streams = tn < 256 / slabs ? tn : 256 / slabs;
-        const dim3 grid((unsigned)(streams * slabs), (unsigned)B), blk(512);
-        const bool pre = act && Ypre;
-        hipStream_t s = (hipStream_t)stream;
-        if (epi_loads && pre) hipLaunchKernelGGL((conv_nn_astat2_kernel<true, true>), grid, blk, 0, s, p, slabs, tn);
-        else if (epi_loads) hipLaunchKernelGGL((conv_nn_astat2_kernel<false, true>), grid, blk, 0, s, p, slabs, tn);
-        else if (pre) hipLaunchKernelGGL((conv_nn_astat2_kernel<true, false>), grid, blk, 0, s, p, slabs, tn);
-        else hipLaunchKernelGGL((conv_nn_astat2_kernel<false, false>), grid, blk, 0, s, p, slabs, tn);
-        return mk_check_launch("mk_conv1x1_nn");
+    case ConvNnKernel::astat2: {
+        const dim3 grid = stationary_grid(256), blk(512);
+        if (epi_loads && pre) hipLaunchKernelGGL((conv_nn_astat2_kernel<true, true>), grid, blk, 0, s, p, slabs, tn64);
+        else if (epi_loads) hipLaunchKernelGGL((conv_nn_astat2_kernel<false, true>), grid, blk, 0, s, p, slabs, tn64);
+        else if (pre) hipLaunchKernelGGL((conv_nn_astat2_kernel<true, false>), grid, blk, 0, s, p, slabs, tn64);
+        else hipLaunchKernelGGL((conv_nn_astat2_kernel<false, false>), grid, blk, 0, s, p, slabs, tn64);
+        break;
     }
-    if (!force_tile && !no_astat && !small_ring && K == 384 && M >= 256 && (long long)M * N * 2 < (1ll << 31) && N >= 64 && !(R && G)) {
-        // weights stationary in registers: 384-channel slabs (4 waves x 3 row tiles; 256-row slabs measured slower), 64-pixel tiles,
-        // persistent grid of 256-thread workgroups
-        const bool epi_loads = R || G;
-        constexpr int tmv = 3;
-        const int kch = epi_loads ? 64 : 128;          // (the 128-channel chunk form of the epilogue-operand variant runs out of registers)
-        const int bm = 128 * tmv;
-        const int slabs = (M + bm - 1) / bm;
-        const long long tn = (N + 63) / 64;
-        const long long streams = tn < 256 / slabs ? tn : 256 / slabs;
-        const dim3 grid((unsigned)(streams * slabs), (unsigned)B), blk(256);
-        const bool pre = act && Ypre;
-        hipStream_t s = (hipStream_t)stream;
+    case ConvNnKernel::astat1: {
+        const dim3 grid = stationary_grid(256), blk(256);
 #define MK_ASTAT(TM_, KCH_)                                                                                              \
     do {                                                                                                                  \
-        if (epi_loads && pre) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, true, true>), grid, blk, 0, s, p, slabs, tn);   \
-        else if (epi_loads) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, false, true>), grid, blk, 0, s, p, slabs, tn);    \
-        else if (pre) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, true, false>), grid, blk, 0, s, p, slabs, tn);          \
-        else hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, false, false>), grid, blk, 0, s, p, slabs, tn);                  \
+        if (epi_loads && pre) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, true, true>), grid, blk, 0, s, p, slabs, tn64);   \
+        else if (epi_loads) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, false, true>), grid, blk, 0, s, p, slabs, tn64);    \
+        else if (pre) hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, true, false>), grid, blk, 0, s, p, slabs, tn64);          \
+        else hipLaunchKernelGGL((conv_nn_astat_kernel<TM_, KCH_, false, false>), grid, blk, 0, s, p, slabs, tn64);                  \
     } while (0)
-        if (kch == 128) MK_ASTAT(3, 128);
-        else MK_ASTAT(3, 64);
+        // 128-channel chunks; 64 with an epilogue operand (the 128-channel chunk form of that variant runs out of registers)
+        if (epi_loads) MK_ASTAT(3, 64);
+        else MK_ASTAT(3, 128);
 #undef MK_ASTAT
-        return mk_check_launch("mk_conv1x1_nn");
+        break;
     }
-    static const bool ring_any_k = [] { const char* e = getenv("MAKANI_AMD_CONV_RINGK"); return !(e && e[0] == '0'); }();
-    if (!force_tile && ((K % 64) == 0 || (ring_any_k && K >= 64)) && M >= 192 && N * 2 * 64 < (1ll << 31) &&
-        (long long)M * lda * 2 < (1ll << 31) && N >= 256) {
-        // ring kernel: persistent grid, one 512-thread workgroup per CU
+    case ConvNnKernel::ring: {
         const bool big = (M % 256 == 0) || M > 576;
         const int bm = big ? 256 : 192;
         const int tm = (M + bm - 1) / bm;
         const long long tn = (N + 255) / 256;
         const long long nt = (long long)tm * tn * B;
         const unsigned grid = (unsigned)(nt < 256 ? nt : 256);
-        if (big) hipLaunchKernelGGL((conv_nn_ring_kernel<4>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p, tm, tn, nt);
-        else hipLaunchKernelGGL((conv_nn_ring_kernel<3>), dim3(grid), dim3(512), 0, (hipStream_t)stream, p, tm, tn, nt);
-        return mk_check_launch("mk_conv1x1_nn");
+        if (big) hipLaunchKernelGGL((conv_nn_ring_kernel<4>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
+        else hipLaunchKernelGGL((conv_nn_ring_kernel<3>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
+        break;
     }
-    // 128 x 256 tile, BK = 64 with one LDS stage (measured 10-15 % faster at 721x1440 than BK = 32 double-buffered,
-    // equal at 240x480; a 128 x 128 tile with two register sets was 10-20 % slower)
-    // BK = 64 with one LDS stage (10-15 % faster at 721x1440 than BK = 32 double-buffered).  Tile 128 x 128 with
-    // 3 workgroups / CU on the internal grid (0.118 ms vs 0.128 for 128 x 256 at 240x480, 768 <- 384; the library:
-    // 0.104), 128 x 256 (longer contiguous row segments) on the full-resolution planes; a 4-workgroup build spills.
-    constexpr int BM = 128;
-    const int tm = (M + BM - 1) / BM;
-    if (N >= (1ll << 19)) {
-        constexpr int BN = 256;
+    case ConvNnKernel::tile: {
+        // BK = 64 with one LDS stage (10-15 % faster at 721x1440 than BK = 32 double-buffered, equal at 240x480).  Tile 128 x 128 with
+        // 3 workgroups / CU on the internal grid (0.118 ms vs 0.128 for 128 x 256 at 240x480, 768 <- 384; the library:
+        // 0.104), 128 x 256 (longer contiguous row segments) on the full-resolution planes; a 4-workgroup build spills.
+        constexpr int BM = 128;
+        const int tm = (M + BM - 1) / BM;
+        const int BN = N >= (1ll << 19) ? 256 : 128;
         const long long tn = (N + BN - 1) / BN;
         const long long nb = (long long)tm * tn * B;
         MK_REQUIRE(nb < (1ll << 31), "conv1x1_nn: grid too large");
-        hipLaunchKernelGGL((conv_nn_kernel<BM, BN, 1, 64, 2>), dim3((unsigned)nb), dim3(NT), 0, (hipStream_t)stream, p, tm, tn);
-    } else {
-        constexpr int BN = 128;
-        const long long tn = (N + BN - 1) / BN;
-        const long long nb = (long long)tm * tn * B;
-        MK_REQUIRE(nb < (1ll << 31), "conv1x1_nn: grid too large");
-        hipLaunchKernelGGL((conv_nn_kernel<BM, BN, 1, 64, 3>), dim3((unsigned)nb), dim3(NT), 0, (hipStream_t)stream, p, tm, tn);
+        if (BN == 256) hipLaunchKernelGGL((conv_nn_kernel<BM, 256, 1, 64, 2>), dim3((unsigned)nb), dim3(NT), 0, s, p, tm, tn);
+        else hipLaunchKernelGGL((conv_nn_kernel<BM, 128, 1, 64, 3>), dim3((unsigned)nb), dim3(NT), 0, s, p, tm, tn);
+        break;
+    }
     }
     return mk_check_launch("mk_conv1x1_nn");
 }
@@ -1956,23 +1912,12 @@ struct WgPlan {
     long long chunk;    // pixels per split
 };
 
-int wgrad_kernel_choice() {      // MAKANI_AMD_WGRAD=tile forces the 128 x 128 tile kernel (A/B measurements)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MAKANI_AMD_WGRAD");
-        v = (e && e[0] == 't') ? 1 : 0;
-    }
-    return v;
-}
-
 WgPlan wgrad_plan(int M, int K, int B, long long N) {
     WgPlan pl{};
     const int big = M > K ? M : K, small = M > K ? K : M;
     // ring kernel: the smaller channel count fits one 384-row tile, the other one is cut into slabs; 32-bit byte
     // offsets inside one batch entry; at least a few pixel tiles per split
-    static const bool ring2d = [] { const char* e = getenv("MAKANI_AMD_WGRAD_2D"); return !(e && e[0] == '0'); }();
-    const bool ok = wgrad_kernel_choice() == 0 && big >= 96 && N * 2 * 384 < (1ll << 31) && N >= 2048;
-    if (ok && (small <= 384 || ring2d)) {
+    if (big >= 96 && N * 2 * 384 < (1ll << 31) && N >= 2048) {
         pl.ring = true;
         int q, pr;                                   // rows of Q (384-row slabs; one slab = held in full) and of P (slabs of tp)
         if (big <= 384) { q = big; pr = small; }

@@ -16,21 +16,11 @@
 // so only the modes the SHT keeps ever touch HBM.  Work items are handed to XCDs in contiguous
 // ranges (xcd_remap) so that lat-adjacent workgroups share an L2 and their RB-float runs of the
 // F-layout merge into full lines before write-back.
-#include <stdlib.h>
 
 #include "fft_common.h"
 
 int mk_fft_fast_dispatch(bool inverse, const void* in, void* out, int dtype, const float* twiddle, int B, int C, int Cp,
                          int nlat, int nlon, int mmax, float w_dc, float w_pos, float w_nyq, const MkFftSeg* seg, void* stream);
-
-static bool use_fast_fft() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("MAKANI_AMD_FFT_GENERIC");
-        v = (e && e[0] == '1') ? 0 : 1;
-    }
-    return v == 1;
-}
 
 namespace {
 
@@ -293,10 +283,8 @@ extern "C" int mk_rfft_rows(const void* x, int x_dtype, float* F, const float* t
     const long long planes = (long long)B * C;     // planes of x
     MK_REQUIRE(mmax >= 1 && mmax <= nlon / 2 + 1, "rfft: mmax=%d out of range for nlon=%d", mmax, nlon);
     MK_REQUIRE(x_dtype == MK_F32 || x_dtype == MK_BF16, "rfft: bad dtype %d", x_dtype);
-    if (use_fast_fft()) {
-        const int frc = mk_fft_fast_dispatch(false, x, F, x_dtype, twiddle, B, C, Cp, nlat, nlon, mmax, w_dc, w_pos, w_nyq, nullptr, stream);
-        if (frc != -1000) return frc;
-    }
+    const int frc = mk_fft_fast_dispatch(false, x, F, x_dtype, twiddle, B, C, Cp, nlat, nlon, mmax, w_dc, w_pos, w_nyq, nullptr, stream);
+    if (frc != -1000) return frc;
     RadixList rl;
     int RB;
     size_t lds;
@@ -330,10 +318,8 @@ extern "C" int mk_irfft_rows(const float* F, void* x, int x_dtype, const float* 
     const long long planes = (long long)B * C;
     MK_REQUIRE(mmax >= 1 && mmax <= nlon / 2 + 1, "irfft: mmax=%d out of range for nlon=%d", mmax, nlon);
     MK_REQUIRE(x_dtype == MK_F32 || x_dtype == MK_BF16, "irfft: bad dtype %d", x_dtype);
-    if (use_fast_fft()) {
-        const int frc = mk_fft_fast_dispatch(true, F, x, x_dtype, twiddle, B, C, Cp, nlat, nlon, mmax, w_dc, w_pos, w_nyq, nullptr, stream);
-        if (frc != -1000) return frc;
-    }
+    const int frc = mk_fft_fast_dispatch(true, F, x, x_dtype, twiddle, B, C, Cp, nlat, nlon, mmax, w_dc, w_pos, w_nyq, nullptr, stream);
+    if (frc != -1000) return frc;
     RadixList rl;
     int RB;
     size_t lds;

@@ -8,12 +8,7 @@
 // and nothing of it is read again before the caches have turned over many times: non-temporal loads and stores, and a grid
 // of (nearly) one 16-byte vector per lane instead of 4 096 resident blocks walking a grid-stride loop.  Same box, 70.8 M
 // floats: 394-414 us (4.8-5.0 TB/s) -> 322 us = 6.15 TB/s (profiles/r03_ab_adamw.txt; the chip's copy rate is 6.3)
-#ifndef MK_ADAMW_NT
-#define MK_ADAMW_NT 1
-#endif
-#ifndef MK_ADAMW_BLOCKS       // cap of the grid, in blocks per CU
-#define MK_ADAMW_BLOCKS 256
-#endif
+#define MK_ADAMW_BLOCKS 256       // cap of the grid, in blocks per CU
 
 namespace {
 constexpr int NT = 256;
@@ -30,17 +25,10 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* __restrict__ p, const 
     const long long n4 = n >> 2;
     const long long stride = (long long)gridDim.x * NT;
     for (long long i = (long long)blockIdx.x * NT + threadIdx.x; i < n4; i += stride) {
-#if MK_ADAMW_NT
         f32x4 pv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
         const f32x4 gv = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g) + i) * gs;
         f32x4 mv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
         f32x4 vv = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
-#else
-        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
-        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * gs;
-        f32x4 mv = reinterpret_cast<f32x4*>(m)[i];
-        f32x4 vv = reinterpret_cast<f32x4*>(v)[i];
-#endif
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             mv[e] = beta1 * mv[e] + (1.f - beta1) * gv[e];
@@ -48,15 +36,9 @@ __global__ __launch_bounds__(NT) void adamw_kernel(float* __restrict__ p, const 
             const float denom = sqrtf(vv[e]) * bc2_rsqrt + eps;
             pv[e] = pv[e] * decay - step * (mv[e] / denom);
         }
-#if MK_ADAMW_NT
         __builtin_nontemporal_store(pv, reinterpret_cast<f32x4*>(p) + i);
         __builtin_nontemporal_store(mv, reinterpret_cast<f32x4*>(m) + i);
         __builtin_nontemporal_store(vv, reinterpret_cast<f32x4*>(v) + i);
-#else
-        reinterpret_cast<f32x4*>(p)[i] = pv;
-        reinterpret_cast<f32x4*>(m)[i] = mv;
-        reinterpret_cast<f32x4*>(v)[i] = vv;
-#endif
     }
     // tail
     if (blockIdx.x == 0) {

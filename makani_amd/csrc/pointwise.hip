@@ -14,15 +14,6 @@
 // non-temporal loads in the passes that read their inputs for the last time (for_chunk<..., LAST>): the backward apply pass
 // of the instance norm 91.6 -> 80.5 us (cold 88 MB planes, same box, profiles/r03_ab_pointwise_nt.txt); the forward apply pass
 // (one input, already cached by the statistics pass) is unchanged
-#ifndef MK_PW_NT
-#define MK_PW_NT 1
-#endif
-#ifndef MK_PW_ST_NT            // A/B knob: plane-sized outputs with the streaming (nt) store policy
-#define MK_PW_ST_NT 0
-#endif
-#ifndef MK_PW_DIAG_VGPR
-#define MK_PW_DIAG_VGPR 0
-#endif
 
 namespace {
 
@@ -47,8 +38,7 @@ struct VecIO<float> {
         f32x4 r;
 #pragma unroll
         for (int i = 0; i < 4; ++i) r[i] = v[i];
-        if constexpr (MK_PW_ST_NT) __builtin_nontemporal_store(r, reinterpret_cast<f32x4*>(p));
-        else *reinterpret_cast<f32x4*>(p) = r;
+        *reinterpret_cast<f32x4*>(p) = r;
     }
     __device__ static __forceinline__ float load1(const float* p) { return *p; }
     __device__ static __forceinline__ void store1(float* p, float v) { *p = v; }
@@ -71,8 +61,7 @@ struct VecIO<u16> {
         uint32_t w[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) w[i] = pack_bf16x2(v[2 * i], v[2 * i + 1]);
-        if constexpr (MK_PW_ST_NT) __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4*>(p));
-        else *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
+        *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
     }
     __device__ static __forceinline__ float load1(const u16* p) { return bf16_to_f32(*p); }
     __device__ static __forceinline__ void store1(u16* p, float v) { *p = f32_to_bf16(v); }
@@ -101,7 +90,7 @@ __host__ __device__ inline long long chunk_len(long long hw, int chunks, int vec
 template <int C>
 using cnt_t = std::integral_constant<int, C>;
 
-// LAST: the inputs are not read again before the caches have turned over -> non-temporal loads (MK_PW_NT)
+// LAST: the inputs are not read again before the caches have turned over -> non-temporal loads
 template <typename T, int NIN, bool LAST = false, typename F>
 __device__ __forceinline__ void for_chunk(long long hw, int chunks, int chunk, const T* p0, const T* p1, F&& f) {
     constexpr int VEC = VecIO<T>::N;
@@ -117,7 +106,7 @@ __device__ __forceinline__ void for_chunk(long long hw, int chunks, int chunk, c
             for (int u = 0; u < U; ++u) {
                 const long long e = base + ((long long)u * NT + threadIdx.x) * VEC;
                 const long long a = e < c1 ? e : c0;
-                if constexpr (LAST && MK_PW_NT) {
+                if constexpr (LAST) {
                     ra[u] = VecIO<T>::load_raw_nt(p0 + a);
                     if (NIN > 1) rb[u] = VecIO<T>::load_raw_nt(p1 + a);
                 } else {
@@ -391,14 +380,7 @@ __global__ __launch_bounds__(NT) void in_bwd_partial(const T* __restrict__ x, co
     const int chunk = blockIdx.x % chunks;
     const int c = (int)(plane % channels);
     const float pb = pre_bias ? pre_bias[c] : 0.f;
-#if MK_PW_DIAG_VGPR
-    // diagnostic build (tools/two_stream_micro.py): the per-plane scalars live in VECTOR registers
-    float mean, rstd;
-    asm volatile("v_mov_b32 %0, %1" : "=v"(mean) : "s"(stats[2 * plane]));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(rstd) : "s"(stats[2 * plane + 1]));
-#else
     const float mean = stats[2 * plane], rstd = stats[2 * plane + 1];
-#endif
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     const T* xp = x + plane * hw;
     const T* gp = gy + plane * hw;
@@ -506,15 +488,9 @@ __global__ __launch_bounds__(NT) void in_bwd_apply(const T* __restrict__ x, cons
 // 88 MB planes (profiles/r06_norm_one_pass.md): 15 slots 44.8 / 92.0 / 145 us, 8 slots 39.9 / 92.4 / 108, 5 slots 40.0 / 92.4 /
 // 97.5 (forward / backward / backward + GELU at 240 x 480 x 384; two-kernel path 52.0 / 97.3 / 107), and at 721 x 1440 8 slots
 // win the forward (0.375 ms) and the plain backward (0.520 vs 0.766 two-kernel), 5 the GELU backward (0.816 vs 0.910)
-#ifndef MK_FUSED_SLOTS_FWD
 #define MK_FUSED_SLOTS_FWD 8
-#endif
-#ifndef MK_FUSED_SLOTS_BWD
 #define MK_FUSED_SLOTS_BWD 8
-#endif
-#ifndef MK_FUSED_SLOTS_BWD_GELU
 #define MK_FUSED_SLOTS_BWD_GELU 5
-#endif
 __host__ __device__ constexpr int fused_slots(int kind) { return kind == 0 ? MK_FUSED_SLOTS_FWD : (kind == 1 ? MK_FUSED_SLOTS_BWD : MK_FUSED_SLOTS_BWD_GELU); }
 constexpr unsigned long long FUSED_SENTINEL = ~0ull;
 

@@ -22,9 +22,6 @@
 
 #include "xsplit.h"
 
-#ifndef MK_X2_ST_NT            // A/B knob: results of the Legendre / dhconv forward and data-gradient GEMMs with the streaming (nt) store policy
-#define MK_X2_ST_NT 0
-#endif
 namespace {
 
 using gemm::BlockCoord;
@@ -41,29 +38,6 @@ constexpr int NT2 = 512;
 #ifndef MK_X2_DIAG
 #define MK_X2_DIAG 0
 #endif
-// structure knobs (tools/ab.py variants)
-#ifndef MK_X2_MIDBAR          // 1: barrier between the two phases of a k-step (strict ping-pong); 0: one barrier per k-step,
-#define MK_X2_MIDBAR 0        //    group 0 = produce then compute, group 1 = compute then produce (soft ping-pong)
-#endif
-#ifndef MK_X2_PRIO            // s_setprio 1 around the MFMA segment: the matrix pipe's wave wins the issue arbitration
-#define MK_X2_PRIO 1          // against its partner's split / store instructions
-#endif
-#ifndef MK_X2_REV             // heaviest batches first for the "<=" triangles (dhconv: l descending)
-#define MK_X2_REV 1
-#endif
-#ifndef MK_X2_DEPTH           // k-steps a global load is issued ahead of its split (1 or 2 staging register sets);
-#define MK_X2_DEPTH 2         // complex kernel.  Measured: 2 = 1 within noise (the kernels are bound by the bytes a CU
-#endif                        // can ingest per clock, not by load latency); the real kernel stays at 1 (2 would spill)
-#ifndef MK_X2_DEPTH_R
-#define MK_X2_DEPTH_R 1
-#endif
-#ifndef MK_X2_WGRAD_NT         // interleaved-complex results (the dhconv weight gradient, read again only by the optimizer at the end
-#define MK_X2_WGRAD_NT 1      // of the step) leave with non-temporal stores: 0.227 -> 0.223 ms, and 283 MB less cache turnover per launch
-#endif
-#ifndef MK_X2_ILV             // limb products issued round-robin over the independent accumulators
-#define MK_X2_ILV 1
-#endif
-
 #if MK_X2_DIAG & 32
 // [group][0 produce, 1 fragment reads, 2 MFMA segment, 3 barrier, 4 prologue, 5 epilogue, 6 whole kernel, 7 waves]
 __device__ unsigned long long g_x2_diag[2][8];
@@ -78,16 +52,10 @@ __device__ unsigned long long g_x2_diag[2][8];
 #define MK_X2_STAMP(k)
 #endif
 
-__device__ __forceinline__ void prio_hi() {
-#if MK_X2_PRIO
-    __builtin_amdgcn_s_setprio(1);
-#endif
-}
-__device__ __forceinline__ void prio_lo() {
-#if MK_X2_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-}
+// s_setprio 1 around the MFMA segment: the matrix pipe's wave wins the issue arbitration against its partner's split / store
+// instructions
+__device__ __forceinline__ void prio_hi() { __builtin_amdgcn_s_setprio(1); }
+__device__ __forceinline__ void prio_lo() { __builtin_amdgcn_s_setprio(0); }
 
 // decode_block with the batch order reversed for the triangles that grow with the batch index: the long-running
 // workgroups start first and the short ones fill the tail of the launch
@@ -105,7 +73,7 @@ __device__ __forceinline__ BlockCoord decode_block2(const MkGemm& p, int tilesM,
     c.khi = p.K;
     c.active = c.b < p.batch;
     if (!c.active) return c;
-    if (MK_X2_REV && (p.tri_mode == MK_TRI_ROW_LE || p.tri_mode == MK_TRI_K_LE)) c.b = p.batch - 1 - c.b;
+    if (p.tri_mode == MK_TRI_ROW_LE || p.tri_mode == MK_TRI_K_LE) c.b = p.batch - 1 - c.b;
     const int tt = c.b / p.inner + p.tri_off;
     switch (p.tri_mode) {
         case MK_TRI_ROW_GE:
@@ -132,7 +100,6 @@ __device__ __forceinline__ BlockCoord decode_block2(const MkGemm& p, int tilesM,
 template <int NP>
 __device__ __forceinline__ void cmma_split(const bf16x8* ar, const bf16x8* ai, const bf16x8* br, const bf16x8* bi,
                                            f32x16& cre, f32x16& cng, f32x16& cim) {
-#if MK_X2_ILV
     constexpr int NPROD = NP == 3 ? 6 : 3;
     constexpr int IA[6] = {1, 0, 2, 0, 1, 0}, IB[6] = {1, 2, 0, 1, 0, 0};      // smallest terms first (as mma_split)
     constexpr int O = NP == 3 ? 0 : 3;
@@ -144,18 +111,11 @@ __device__ __forceinline__ void cmma_split(const bf16x8* ar, const bf16x8* ai, c
         cng = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ai[a], bi[b], cng, 0, 0, 0);
         cim = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ai[a], br[b], cim, 0, 0, 0);
     }
-#else
-    cre = mma_split<NP>(ar, br, cre);
-    cng = mma_split<NP>(ai, bi, cng);
-    cim = mma_split<NP>(ar, bi, cim);
-    cim = mma_split<NP>(ai, br, cim);
-#endif
 }
 
 // two real 32 x 32 x 16 tile updates sharing the A fragment
 template <int NP>
 __device__ __forceinline__ void rmma_split2(const bf16x8* a, const bf16x8* b0, const bf16x8* b1, f32x16& c0, f32x16& c1) {
-#if MK_X2_ILV
     constexpr int NPROD = NP == 3 ? 6 : 3;
     constexpr int IA[6] = {1, 0, 2, 0, 1, 0}, IB[6] = {1, 2, 0, 1, 0, 0};
     constexpr int O = NP == 3 ? 0 : 3;
@@ -164,10 +124,6 @@ __device__ __forceinline__ void rmma_split2(const bf16x8* a, const bf16x8* b0, c
         c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[IA[O + q]], b0[IB[O + q]], c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[IA[O + q]], b1[IB[O + q]], c1, 0, 0, 0);
     }
-#else
-    c0 = mma_split<NP>(a, b0, c0);
-    c1 = mma_split<NP>(a, b1, c1);
-#endif
 }
 // explicit global address space on the staging loads: a pointer that may be either an operand address or the zero
 // block is otherwise treated as generic and loaded with flat_load (which also ties up the LDS counter)
@@ -417,7 +373,9 @@ __global__ __launch_bounds__(NT2) void xcgemm2_kernel(const MkGemm p, int tilesM
     const int kt0 = c.klo / BK, kt1 = (c.khi + BK - 1) / BK;
     const int nk = kt1 - kt0;
     const int a_rmax = A_KC ? c.Meff : p.M;
-    constexpr int D = TALL ? 1 : MK_X2_DEPTH;               // staging register sets: tile t rides in set t % D
+    // staging register sets (tile t rides in set t % D) = k-steps a global load is issued ahead of its split.  2 measured equal to 1
+    // within noise: the kernels are bound by the bytes a CU can ingest per clock, not by load latency
+    constexpr int D = TALL ? 1 : 2;
     Stage2<BM, A_KC, BM / 4, TALL> sar[D], sai[D];
     Stage2<BN, B_KC, BN / 4, TALL> sbr[D], sbi[D];          // B_ILV: sbr carries both parts, sbi is unused
 #pragma unroll
@@ -537,11 +495,6 @@ __global__ __launch_bounds__(NT2) void xcgemm2_kernel(const MkGemm p, int tilesM
     }
     __syncthreads();
     auto step = [&](auto set, int i) __attribute__((always_inline)) {
-#if MK_X2_MIDBAR
-        if (grp == 0) { if (!(MK_X2_DIAG & 2)) compute(i & 1); } else produce(set, i);
-        __syncthreads();
-        if (grp == 1) { if (!(MK_X2_DIAG & 2)) compute(i & 1); } else produce(set, i);
-#else
         // one barrier per k-step; the groups run the two segments in opposite order, so that on every SIMD one wave
         // starts on the matrix pipe while its partner starts on the VALU / memory path.
         // (`grp` is a per-lane value to the compiler, so the two orders are laid out one after the other under exec masks;
@@ -563,7 +516,6 @@ __global__ __launch_bounds__(NT2) void xcgemm2_kernel(const MkGemm p, int tilesM
             produce(set, i);
             MK_X2_STAMP(0);
         }
-#endif
         __syncthreads();
         MK_X2_STAMP(3);
     };
@@ -592,15 +544,10 @@ __global__ __launch_bounds__(NT2) void xcgemm2_kernel(const MkGemm p, int tilesM
                 }
                 sq = fmaf(vr, vr, fmaf(vi, vi, sq));
                 if (p.c_col == 2) {          // interleaved complex C: one 8-byte store per entry
-#if MK_X2_WGRAD_NT
+                    // (the dhconv weight gradient, read again only by the optimizer at the end of the step: non-temporal,
+                    //  0.227 -> 0.223 ms and 283 MB less cache turnover per launch)
                     typedef float f32x2_t __attribute__((ext_vector_type(2)));
                     __builtin_nontemporal_store(f32x2_t{vr, vi}, reinterpret_cast<f32x2_t*>(dr));
-#else
-                    *reinterpret_cast<float2*>(dr) = make_float2(vr, vi);
-#endif
-                } else if constexpr (MK_X2_ST_NT) {
-                    __builtin_nontemporal_store(vr, dr);
-                    __builtin_nontemporal_store(vi, di);
                 } else {
                     *dr = vr;
                     *di = vi;
@@ -715,7 +662,7 @@ __global__ __launch_bounds__(NT2) void xgemm2_kernel(const MkGemm p, const PreA 
 
     const int kt0 = c.klo / BK, kt1 = (c.khi + BK - 1) / BK;
     const int nk = kt1 - kt0;
-    constexpr int D = MK_X2_DEPTH_R;
+    constexpr int D = 1;                                    // staging register sets (2 would spill)
     Stage2<BN, false, NARROW ? NCT * 8 : BN / 4> sb[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) sb[d].init(Bb, p.b_col, p.b_k, c.j0, p.N, tid);
@@ -794,15 +741,9 @@ __global__ __launch_bounds__(NT2) void xgemm2_kernel(const MkGemm p, const PreA 
         ld(S0{}, kt0);
         st(S0{}, 0);
         if (nk > 1) ld(S1{}, kt0 + 1);
-        if (D == 2 && nk > 2) ld(S0{}, kt0 + 2);
     }
     __syncthreads();
     auto step = [&](auto set, int i) __attribute__((always_inline)) {
-#if MK_X2_MIDBAR
-        if (grp == 0) { if (!(MK_X2_DIAG & 2)) compute(i & 1); } else produce(set, i);
-        __syncthreads();
-        if (grp == 1) { if (!(MK_X2_DIAG & 2)) compute(i & 1); } else produce(set, i);
-#else
         // one barrier per k-step; the groups run the two segments in opposite order, so that on every SIMD one wave
         // starts on the matrix pipe while its partner starts on the VALU / memory path
         if (grp == 0) {
@@ -812,7 +753,6 @@ __global__ __launch_bounds__(NT2) void xgemm2_kernel(const MkGemm p, const PreA 
             if (!(MK_X2_DIAG & 2)) compute(i & 1);
             produce(set, i);
         }
-#endif
         __syncthreads();
     };
     for (int i = 0; i < nk; i += 2) {                       // step i splits tile i + 1, which rides in set (i + 1) % D
@@ -847,8 +787,7 @@ __global__ __launch_bounds__(NT2) void xgemm2_kernel(const MkGemm p, const PreA 
                         float* dst = Cb + (long long)row * p.c_row + col;
                         float val = acc[n >> 1][n & 1][r];
                         if (p.beta) val += *dst;
-                        if constexpr (MK_X2_ST_NT) __builtin_nontemporal_store(val, dst);
-                        else *dst = val;
+                        *dst = val;
                     }
                 }
             }
@@ -868,20 +807,23 @@ __global__ __launch_bounds__(NT2) void xgemm2_kernel(const MkGemm p, const PreA 
                     float* dst = Cb + (long long)row * p.c_row + col;
                     float val = acc[j][n][r];
                     if (p.beta) val += *dst;
-                    if constexpr (MK_X2_ST_NT) __builtin_nontemporal_store(val, dst);
-                    else *dst = val;
+                    *dst = val;
                 }
             }
         }
     }
 }
 
+// more than 128 rows and a k-contiguous A (the dhconv forward / data gradient: A = the coefficients of one degree, rows = orders):
+// the 256 x 128 form.  MAKANI_AMD_X2_TALL=0 keeps the 128 x 128 tile everywhere
+bool cplx2_tall(const MkGemm* g, bool a_kc) {
+    static const bool tall_ok = [] { const char* e = getenv("MAKANI_AMD_X2_TALL"); return !(e && e[0] == '0'); }();
+    return tall_ok && a_kc && g->M > 128;
+}
+
 template <int NP>
 int launch_cplx2(const MkGemm* g, bool a_kc, bool b_kc, bool b_ilv, hipStream_t s, float* ssq = nullptr) {
-    // more than 128 rows and a k-contiguous A (the dhconv forward / data gradient: A = the coefficients of one degree, rows = orders):
-    // the 256 x 128 form.  MAKANI_AMD_X2_TALL=0 keeps the 128 x 128 tile everywhere
-    static const bool tall_ok = [] { const char* e = getenv("MAKANI_AMD_X2_TALL"); return !(e && e[0] == '0'); }();
-    const bool tall = tall_ok && a_kc && g->M > 128;
+    const bool tall = cplx2_tall(g, a_kc);
     const int BM = tall ? 256 : 128, BN = 128;
     const int tm = (g->M + BM - 1) / BM, tn = (g->N + BN - 1) / BN;
     const long long nb = (long long)((g->batch + MK_NUM_XCD - 1) / MK_NUM_XCD) * MK_NUM_XCD * tm * tn;
@@ -942,8 +884,7 @@ extern "C" int mk_cgemm_split2_batched(const MkGemm* g, int limbs, void* stream)
 
 // grid of launch_cplx2 (one partial per workgroup)
 static long long cplx2_blocks(const MkGemm* g, bool a_kc) {
-    static const bool tall_ok = [] { const char* e = getenv("MAKANI_AMD_X2_TALL"); return !(e && e[0] == '0'); }();
-    const bool tall = tall_ok && a_kc && g->M > 128;
+    const bool tall = cplx2_tall(g, a_kc);
     const int BM = tall ? 256 : 128, BN = 128;
     const int tm = (g->M + BM - 1) / BM, tn = (g->N + BN - 1) / BN;
     return (long long)((g->batch + MK_NUM_XCD - 1) / MK_NUM_XCD) * MK_NUM_XCD * tm * tn;

@@ -54,12 +54,9 @@ def gemm_mode() -> str:
         return "x6"
 
 
-# Kernel generation of the split engine: "2" = the ping-pong kernels of csrc/xgemm2.hip (512-thread workgroups, double-buffered
-# limb images, pre-split Legendre matrices) wherever they apply; the real kernel of csrc/xgemm.hip serves the rest (operands
-# that are both split on the fly: the fp32 channel GEMMs of the parity runs).
-GEMM_GEN = "2"          # (module attribute, not an environment switch: tools may set "1" to time the first-generation real kernel)
-
-
+# The split engine runs the ping-pong kernels of csrc/xgemm2.hip (512-thread workgroups, double-buffered limb images, pre-split
+# Legendre matrices) wherever they apply; the real kernel of csrc/xgemm.hip serves the rest (operands that are both split on the
+# fly: the fp32 channel GEMMs of the parity runs).
 def _run_gemm(g, cplx, what, mode=None, a_limbs=None, band=None, ssq=None):
     """``a_limbs``: the constant A operand of a real GEMM already split into bf16 limb planes (``limb_planes``);
     ``band`` = (lo, hi, mode): its numerical band per batch (``polar_band``); ``ssq``: buffer for the per-workgroup sums of
@@ -71,19 +68,19 @@ def _run_gemm(g, cplx, what, mode=None, a_limbs=None, band=None, ssq=None):
         rc = (L.mk_cgemm_batched if cplx else L.mk_sgemm_batched)(C.byref(g), stream())
     else:
         limbs = 3 if mode == "x6" else 2
-        if GEMM_GEN == "2" and cplx:
+        if cplx:
             if ssq is not None:
                 rc = L.mk_cgemm_split2_batched_ssq(C.byref(g), limbs, ptr(ssq), stream())
             else:
                 rc = L.mk_cgemm_split2_batched(C.byref(g), limbs, stream())
-        elif GEMM_GEN == "2" and a_limbs is not None:
+        elif a_limbs is not None:
             pl = a_limbs
             lo, hi, bm = band if band is not None else (None, None, 0)
             rc = L.mk_sgemm_presplit_batched(C.byref(g), ptr(pl), pl.stride(0), pl.stride(1), pl.stride(2), limbs,
                                              ptr(lo), ptr(hi), bm, stream())
         else:
             assert ssq is None
-            rc = (L.mk_cgemm_split_batched if cplx else L.mk_sgemm_split_batched)(C.byref(g), limbs, stream())
+            rc = L.mk_sgemm_split_batched(C.byref(g), limbs, stream())
     check(rc, what)
 
 
@@ -391,7 +388,7 @@ def _exec_band(L, M, m_off, nlat, band, lat_gran, rows_tri):
 
 
 def _presplit_ok() -> bool:
-    return GEMM_GEN == "2" and gemm_mode() != "fp32"
+    return gemm_mode() != "fp32"
 
 
 def legendre_analysis(F: torch.Tensor, matT: torch.Tensor, L: int, m_off: int = 0, lat_major: bool = False,
@@ -567,7 +564,7 @@ def dhconv_wgrad(S: torch.Tensor, gT: torch.Tensor, B: int, tri_off: int = 0, gr
         gW = torch.empty((L, 2, cip, cop), dtype=torch.float32, device=S.device)
         cdesc = dict(c_batch=2 * cip * cop, c_row=cop, c_im=cip * cop)
     # the whole gradient from ONE launch (native order, one sample, one group): the launch also sums its squares
-    want_ssq = GRAD_SSQ and native and B == 1 and grp is None and GEMM_GEN == "2" and gemm_mode() != "fp32"
+    want_ssq = GRAD_SSQ and native and B == 1 and grp is None and gemm_mode() != "fp32"
     grad_ssq_drop(gW)
     for b in range(B):
         g = _gemm(A=S.data_ptr() + 4 * (b * xld + a_off), B=gT.data_ptr() + 4 * (b * yld + c_off), C=gW.data_ptr(),

@@ -512,6 +512,40 @@ def test_c_abi_host_side_planning_functions():
     assert L.mk_conv1x1_wgrad_workspace(384, 384, 1, 1038240) % (384 * (384 + 1)) == 0
 
 
+def test_channel_gemm_kernel_choice_for_the_shapes_of_the_networks(tmp_path):
+    """csrc/conv1x1_plan.h (plain C++, compiled here for the host): the kernel mk_conv1x1_nn launches for every channel GEMM
+    of the networks — full grids and the shards of one rank — with each epilogue, and under the two overrides"""
+    import subprocess
+    from makani_amd import build
+    src = tmp_path / "plan.cpp"
+    src.write_text('#include "conv1x1_plan.h"\nextern "C" int plan(int M, int K, int lda, int B, long long N, int pre, int r, int g, int a2) '
+                   '{ return (int)conv_nn_plan(M, K, lda, B, N, pre, r, g, a2); }\n')
+    so = str(tmp_path / "plan.so")
+    subprocess.check_call([build.HIPCC, "-x", "c++", "-std=c++17", "-shared", "-fPIC", "-I", build.CSRC, str(src), "-o", so])
+    L = ctypes.CDLL(so)
+    L.plan.argtypes = [ctypes.c_int] * 4 + [ctypes.c_longlong] + [ctypes.c_int] * 4
+    ASTAT73, ASTAT2, ASTAT1, RING, TILE = range(5)
+    EPI = {"plain": (0, 0, 0), "bias+gelu+pre": (1, 0, 0), "skip": (0, 1, 0), "gelu'": (0, 0, 1)}
+
+    def plan(M, K, N, epi, lda=None, a2=-1):
+        return L.plan(M, K, lda or K, 1, N, *EPI[epi], a2)
+    for N in (115200, 1038240, 14400, 32400):
+        shard = N <= 32768
+        for epi in EPI:
+            assert plan(384, 384, N, epi) == (RING if shard and epi != "bias+gelu+pre" else ASTAT2), (N, epi)
+            assert plan(768, 384, N, epi) == ASTAT2, (N, epi)
+            assert plan(384, 768, N, epi) == RING, (N, epi)
+            assert plan(384, 73, N, epi, lda=80) == ASTAT73, (N, epi)
+            assert plan(73, 384, N, epi) == TILE, (N, epi)
+            # MAKANI_AMD_ASTAT2=0: the one-group kernel wherever the two-group kernel ran; =1: the two-group kernel on shards too
+            assert plan(384, 384, N, epi, a2=0) == (RING if shard and epi != "bias+gelu+pre" else ASTAT1), (N, epi)
+            assert plan(768, 384, N, epi, a2=0) == ASTAT1 and plan(384, 384, N, epi, a2=1) == ASTAT2, (N, epi)
+    # a skip operand next to a stored pre-activation has no 73-channel stationary form; two epilogue operands none at all
+    assert L.plan(384, 73, 80, 1, 115200, 1, 1, 0, -1) == RING and L.plan(384, 384, 384, 1, 115200, 0, 1, 1, -1) == RING
+    # byte offsets of one batch entry past 32 bits, fewer than 256 rows, fewer than 64 input channels
+    assert plan(1536, 384, 1038240, "plain") == RING and plan(128, 384, 115200, "plain") == TILE and plan(384, 32, 115200, "plain") == TILE
+
+
 def test_fused_schedule_plan_invariants():
     """makani_amd.dist_pipeline.Plan (host logic of the fused h x w exchange schedule): the plane blocks / sub-blocks partition
     the planes, every slab offset is a multiple of 4 floats (16-byte vectors), every rank of a configuration cuts the same

@@ -106,11 +106,11 @@ def test_fft_lds_plans_of_the_source_are_the_modelled_ones_and_consistent():
     fm = _fft_model()
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "makani_amd", "csrc", "fft_fast.hip")).read()
     found = {}
-    for m in re.finditer(r"struct LdsPlan<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false), true> \{[^\n]*\n\s*static constexpr int "
+    for m in re.finditer(r"struct LdsPlan<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false)> \{[^\n]*\n\s*static constexpr int "
                          r"LS0 = (\d+), LS1 = (\d+), LS2 = (\d+), LS3 = (\d+), D1 = (\d+), D2 = (\d+), LPR1 = (\d+), LPR2 = (\d+), LPR3 = (\d+);\n"
-                         r"\s*static constexpr bool SWAP = (true|false|MK_FFT_SWAP != 0);", src):
+                         r"\s*static constexpr bool SWAP = (true|false);", src):
         g = m.groups()
-        found[(int(g[0]), int(g[4]), g[6] == "true")] = ([int(x) for x in g[7:11]], [0, int(g[11]), int(g[12])], [int(x) for x in g[13:16]], g[16] == "true")      # (MK_FFT_SWAP defaults to 0)
+        found[(int(g[0]), int(g[4]), g[6] == "true")] = ([int(x) for x in g[7:11]], [0, int(g[11]), int(g[12])], [int(x) for x in g[13:16]], g[16] == "true")
     shipped = {(720, 16, False): fm.KERNELS["rfft 1440 bf16 (16 rows, 512 threads)"][2], (720, 16, True): fm.KERNELS["irfft 1440 pruned (16 rows, 512 threads)"][2],
                (240, 16, False): fm.KERNELS["rfft 480 bf16 (one half: 16 rows, 256 threads)"][2], (240, 32, True): fm.KERNELS["irfft 480 (32 rows, 512 threads)"][2]}
     assert set(found) == set(shipped)

@@ -1,5 +1,5 @@
 """Outputs of the specialised FFT kernels on seeded inputs, written to a file: run once per library build (MAKANI_AMD_LIB) and
-compare — a change of the LDS layouts (csrc/fft_fast.hip LdsPlan, MK_FFT_LDSPLAN=0 = one layout) must leave every bit alone.
+compare — a change of the LDS layouts (csrc/fft_fast.hip LdsPlan) must leave every bit alone.
    python tools/fft_plan_check.py out.pt            # writes
    python tools/fft_plan_check.py a.pt b.pt         # compares two files"""
 import math

@@ -146,8 +146,8 @@ def cold():
 
 
 def conv():
-    """forward / data-gradient channel GEMM: HIP kernel (MAKANI_AMD_CONV_NN=tile: the 128-row tile kernel instead of the
-    ring kernel) against the library GEMM, plain and with the fused epilogues; each result checked against fp32"""
+    """forward / data-gradient channel GEMM: HIP kernel against the library GEMM, plain and with the fused epilogues; each
+    result checked against fp32"""
     per_step = {(768, 384, 721): 2, (384, 768, 721): 2, (384, 384, 721): 8, (768, 384, 240): 14, (384, 768, 240): 14, (384, 384, 240): 14}
     tot_hip = tot_lib = 0.0
     for (M, K, H, W) in ((768, 384, 721, 1440), (384, 768, 721, 1440), (384, 384, 721, 1440), (768, 384, 240, 480),
@@ -187,7 +187,7 @@ def conv():
 
 def wgrad():
     """channel-GEMM weight gradient: the nine shapes of the train step (+ ragged / batched ones), checked against an fp32
-    GEMM of the same bf16 operands, then timed.  MAKANI_AMD_WGRAD=tile selects the 128 x 128 tile kernel."""
+    GEMM of the same bf16 operands, then timed."""
     shapes = [(768, 384, 1, 721, 1440), (384, 768, 1, 721, 1440), (384, 384, 1, 721, 1440), (384, 73, 1, 721, 1440),
               (73, 384, 1, 721, 1440), (73, 73, 1, 721, 1440), (768, 384, 1, 240, 480), (384, 768, 1, 240, 480),
               (384, 384, 1, 240, 480), (384, 200, 2, 91, 184), (300, 384, 1, 37, 72), (768, 384, 2, 60, 124)]
