@@ -108,6 +108,24 @@ int mk_sgemm_presplit_batched(const MkGemm* g, const void* a_planes, long long p
                               long long pl_k, int limbs, const int* band_lo, const int* band_hi, int band_mode,
                               void* stream);
 
+/* ---- vector Legendre stage (csrc/vlegendre.hip) --------------------------------
+ * mk_vlegendre: the Legendre stage of th.RealVectorSHT / th.InverseRealVectorSHT [torch-harmonics, un-vendored; call sites
+ *   makani/utils/losses/base_loss.py:461-469,547-554] and its autograd, one launch per direction.
+ *   A vector field of P pairs is a scalar F / S tensor whose rows are (component, pair), Rp = P rounded up to 32 rows per
+ *   component: F (orders, nlat, 2, 2 Rp), S (L, orders, 2, 2 Rp).  planes0 / planes1: limb planes (as for
+ *   mk_sgemm_presplit_batched: [plane][order][k][row], row contiguous) of dP/dtheta and m P/sin(theta), both over
+ *   sqrt(l (l + 1)).  mode 0 analysis (rows = L, K = nlat; planes = weighted matrices, [lat][l]):
+ *       s = A0 U - i A1 V,  t = i A1 U + A0 V;
+ *   mode 1 synthesis (rows = nlat, K = L; planes [l][lat]):  U = A0 s - i A1 t,  V = i A1 s + A0 t;
+ *   mode 2 analysis that forms s only: out is S (L, orders, 2, Rp);
+ *   mode 3 synthesis with t = 0: in is S (L, orders, 2, Rp) (the gradient of a scalar field).
+ *   Modes 1 / 0 with the transposed matrices are the transposed maps of modes 0 / 1, modes 3 / 2 those of 2 / 3.
+ *   band_lo / band_hi (device int[orders], optional): the latitude band outside of which BOTH matrices vanish; analysis
+ *   clips the latitude sum, synthesis writes exact zeros outside.  Rows l < m + tri_off are skipped in 32-row steps. */
+int mk_vlegendre(const void* planes0, const void* planes1, long long pl_stride, long long pl_batch, long long pl_k,
+                 int limbs, const float* in, float* out, int mode, int rows, int K, int orders, int Rp, int tri_off,
+                 const int* band_lo, const int* band_hi, void* stream);
+
 /* ---- longitude FFTs ----------------------------------------------------------
  * mk_rfft_rows: x[row][lat][lon] (f32|bf16)  ->  F-layout, modes m < mmax:
  *     X_m = w_m * sum_n x_n exp(-2 pi i m n / nlon),  w = (w_dc, w_pos, w_nyq)

@@ -101,6 +101,77 @@ def legendre_matrix(mmax, lmax, theta, norm="ortho", inverse=False, csphase=True
     return P
 
 
+def vector_legendre_matrices(mmax, lmax, theta, norm="ortho", inverse=False, csphase=True):
+    """W[c, m, l, k] (fp64, (2, mmax, lmax, nlat)): the two latitude functions of the vector spherical harmonic transforms,
+
+        W[0] = d P_l^m / d theta / sqrt(l (l + 1))          W[1] = m P_l^m / sin(theta) / sqrt(l (l + 1))
+
+    with P_l^m of ``legendre_matrix`` (same ``norm`` / ``inverse`` / ``csphase``); row l = 0 is zero (a constant has no
+    gradient).  Convention (the orthonormal vector harmonics; the published torch-harmonics ``RealVectorSHT`` pair is
+    not available to compare against, so the convention is pinned by mathematics in tests/test_vsht_cpu.py):
+    with Y_lm = P_l^m(theta) e^{i m phi},
+
+        Psi_lm = grad Y_lm / sqrt(l (l + 1))   (spheroidal),      Phi_lm = r x Psi_lm   (toroidal),
+
+    a tangent field with components (component 0 = colatitudinal theta-hat, pointing SOUTH; component 1 = azimuthal
+    phi-hat, pointing EAST) is  sum_lm  s_lm Psi_lm + t_lm Phi_lm, i.e. per order m and with U, V the longitude spectra
+    of the two components (Psi = (W0, i W1), Phi = (-i W1, W0))
+
+        U = W0 s - i W1 t             s = W0^T U - i W1^T V
+        V = i W1 s + W0 t             t = i W1^T U + W0^T V          (^T: quadrature over latitude)
+
+    so that ``ivsht([f_lm sqrt(l (l + 1)), 0])`` is the surface gradient (d/dtheta, 1/sin(theta) d/dphi) of the scalar
+    field with coefficients f_lm, a field with s = 0 is divergence free and one with t = 0 curl free.  The sign of the
+    toroidal part: t_lm multiplies +Phi_lm = +r x Psi_lm (r x theta-hat = phi-hat), so the stream function psi with
+    coefficients t_lm / sqrt(l (l + 1)) gives the field r x grad psi and the vorticity  -sum sqrt(l (l + 1)) t_lm Y_lm.
+
+    Both functions are evaluated WITHOUT a division by sin(theta) (the equiangular grids have nodes at both poles), from
+    the orthonormal functions of the neighbouring orders (ladder operators; Condon-Shortley phase included):
+
+        d P_l^m / d theta  = ( sqrt((l - m)(l + m + 1)) P_l^{m+1} - sqrt((l + m)(l - m + 1)) P_l^{m-1} ) / 2
+        m P_l^m / sin      = - sqrt((2l + 1) / (2l - 1)) ( sqrt((l - m)(l - m - 1)) P_{l-1}^{m+1}
+                                                           + sqrt((l + m)(l + m - 1)) P_{l-1}^{m-1} ) / 2
+    with P_l^{-1} = -P_l^1."""
+    n = max(mmax + 1, lmax)
+    P = legendre_matrix(n, n, theta, norm="ortho", inverse=False, csphase=True)       # (order, degree, latitude)
+    nk = len(theta)
+    W = np.zeros((2, mmax, lmax, nk))
+    l = np.arange(lmax, dtype=np.float64)[:, None]
+    Pl = P[:, :lmax]                                                                   # degree l
+
+    def below(m):                                                                      # P_{l-1}^m as a function of l
+        out = np.zeros((lmax, nk))
+        out[1:] = P[m, : lmax - 1]
+        return out
+
+    for m in range(mmax):
+        up = Pl[m + 1]
+        dn = Pl[m - 1] if m > 0 else -Pl[1]
+        cp = np.sqrt(np.maximum((l - m) * (l + m + 1), 0.0))
+        cm = np.sqrt(np.maximum((l + m) * (l - m + 1), 0.0))
+        W[0, m] = 0.5 * (cp * up - cm * dn)
+        if m > 0:
+            ap = np.sqrt(np.maximum((l - m) * (l - m - 1), 0.0))
+            am = np.sqrt(np.maximum((l + m) * (l + m - 1), 0.0))
+            f = np.sqrt((2 * l + 1) / np.maximum(2 * l - 1, 1.0))
+            W[1, m] = -0.5 * f * (ap * below(m + 1) + am * below(m - 1))
+        W[:, m, : min(m, lmax)] = 0.0                                                  # l < m
+    ll = np.arange(lmax, dtype=np.float64)
+    scale = np.zeros(lmax)
+    scale[1:] = 1.0 / np.sqrt(ll[1:] * (ll[1:] + 1.0))
+    nf = 1.0 if norm == "ortho" else math.sqrt(4 * math.pi)                            # as legendre_matrix
+    if inverse:
+        nf = 1.0 / nf
+    scale *= nf
+    if norm == "schmidt":
+        f = np.sqrt(2.0 * ll + 1.0)
+        scale = scale * f if inverse else scale / f
+    W *= scale[None, None, :, None]
+    if not csphase:
+        W[:, 1::2] *= -1.0
+    return W
+
+
 def factorize_half(nlon):
     """Radix list (4s first, then 2, 3, 5, small primes) whose product is nlon // 2."""
     if nlon % 2:

@@ -648,3 +648,216 @@ class SpectralCRPSLoss(SpectralLpLoss):
         if self.spatial_distributed:
             crps = thd.reduce_from_spatial_region(crps)
         return crps
+
+
+# --------------------------------------------------------------------------- #
+# ensemble CRPS of gradients and of the wind field's vorticity / divergence decomposition
+# (makani/utils/losses/crps_loss.py:640-1019, base classes base_loss.py:427-585)
+# --------------------------------------------------------------------------- #
+def get_wind_channels(channel_names):
+    """``makani/utils/features.py:83-94``: every ``uX`` with a ``vX`` in the list gives the index pair (u, v)"""
+    out = []
+    for c, ch in enumerate(channel_names):
+        if ch[0] == "u" and ("v" + ch[1:]) in channel_names:
+            out += [c, channel_names.index("v" + ch[1:])]
+    return out
+
+
+_SURFACE_01 = ("u10m", "v10m", "u100m", "v100m", "tp", "sp", "msl", "tcwv", "sst")
+
+
+def channel_weighting(channel_names, channel_weight_type, time_diff_scale=None):
+    """the "constant", "auto" and "new auto" rules of ``base_loss.py:33-72`` (pressure-level channels weighted by their level);
+    the tabulated "custom" weights and the time-difference scalings are not carried here"""
+    w = torch.ones(len(channel_names), dtype=torch.float32)
+    if channel_weight_type in ("auto", "new auto"):
+        new = channel_weight_type == "new auto"
+        for c, chn in enumerate(channel_names):
+            if chn in _SURFACE_01:
+                w[c] = 0.1
+            elif chn in ("t2m", "2d"):
+                w[c] = 2.0 if new else 1.0
+            elif chn[0] in "zuvtrq":
+                w[c] = max(0.3, 0.001 * float(chn[1:])) if new else 0.001 * float(chn[1:])
+            else:
+                w[c] = 0.01
+    elif channel_weight_type != "constant":
+        raise NotImplementedError(f"channel weighting {channel_weight_type!r} is not built on the HIP path (constant, auto, new auto)")
+    if time_diff_scale is not None:
+        raise NotImplementedError("time-difference scaling of the channel weights is not built on the HIP path")
+    return w
+
+
+class _EnsembleGridLoss(nn.Module):
+    """what ``GradientCRPSLoss`` and ``VortDivCRPSLoss`` share: constructor checks, quadrature, the score on the grid"""
+
+    def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
+                 ensemble_distributed, ensemble_weights, alpha, eps):
+        super().__init__()
+        if spatial_distributed or ensemble_distributed:
+            from . import comm as _comm
+            _comm.autodetect()
+            if (spatial_distributed and _comm.is_distributed("spatial") and _comm.get_size("spatial") > 1) or \
+                    (ensemble_distributed and _comm.is_distributed("ensemble") and _comm.get_size("ensemble") > 1):
+                raise NotImplementedError(f"{type(self).__name__}: the distributed vector transforms are not built yet "
+                                          "(spatial_distributed / ensemble_distributed with a group larger than one)")
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.spatial_distributed = self.ensemble_distributed = False
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=False)
+        if tuple(crop_shape) != tuple(img_shape):
+            raise NotImplementedError("the vector-transform losses score the whole sphere (crop_shape == img_shape)")
+        if crps_type not in ("skillspread", "naive skillspread") and alpha < 1.0:
+            raise NotImplementedError("The alpha parameter (almost fair CRPS factor) is only supported for the skillspread kernels.")
+        if ensemble_weights is not None and crps_type != "cdf":            # crps_loss.py:810-811 (the gauss branch cannot run there)
+            raise NotImplementedError("currently only constant ensemble weights are supported")
+        _check_finite_weights(ensemble_weights)
+        self.crps_type, self.alpha, self.eps = crps_type, alpha, eps
+        self.register_buffer("ensemble_weights", None if ensemble_weights is None else ensemble_weights.float().reshape(-1).contiguous(),
+                             persistent=False)
+        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
+    @staticmethod
+    def _check(forecasts, observations, spatial_weights):
+        if forecasts.dim() != 5:
+            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
+        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
+            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
+                             f"observations (found {observations.dim()}).")
+        if not forecasts.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+
+    def _score(self, forecasts, observations, spatial_weights):
+        """forecasts (B, E, C, H, W), observations (B, C, H, W) -> (B, C), as ``CRPSLoss.forward``"""
+        if self.crps_type not in ("cdf", "skillspread", "gauss"):              # what the reference's forward knows
+            raise ValueError(f"Unknown CRPS crps_type {self.crps_type}")
+        B, E, Cc, H, W = forecasts.shape
+        if E == 1:
+            return self.quadrature.lp(forecasts.squeeze(1), observations, spatial_weights, 1.0).reshape(B, Cc)
+        w = spatial_weights.expand(B, Cc, H, W) if spatial_weights is not None else None
+        return CrpsFn.apply(forecasts, observations, self.quad_weight_split.reshape(-1), w, _CRPS_TYPES[self.crps_type], self.alpha,
+                            self.eps, _ens_w(self.ensemble_weights, E, self.crps_type))
+
+
+class GradientCRPSLoss(_EnsembleGridLoss):
+    """``GradientCRPSLoss`` of ``makani/utils/losses/crps_loss.py:640-844`` ("ensemble_gradient_crps"): the ensemble CRPS of the
+    surface gradient of every channel — ``absolute=True``: of its magnitude, (B, C); ``False``: of both components, (B, 2 C) in
+    the order (c, component).  Scalar analysis (HIP SHT), then the vector synthesis with a ZERO toroidal part
+    (``InverseRealVectorSHT.synthesis(t_zero=True)``: nothing is stored or multiplied for it), in fp32 whatever the autocast
+    state; score and quadrature are the kernels of ``CRPSLoss``.  Serial only."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, crps_type: str = "skillspread",
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
+                 ensemble_weights: Optional[torch.Tensor] = None, absolute: Optional[bool] = True, alpha: Optional[float] = 1.0,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
+                         ensemble_distributed, ensemble_weights, alpha, eps)
+        from .sht import RealSHT, InverseRealVectorSHT
+        self.absolute = absolute
+        self.sht = RealSHT(*img_shape, lmax=lmax, mmax=lmax, grid=grid_type)
+        self.ivsht = InverseRealVectorSHT(self.sht.nlat, self.sht.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+
+    @property
+    def n_channels(self):
+        return len(self.channel_names) * (1 if self.absolute else 2)
+
+    @staticmethod
+    def expand_channel_weights(chw):
+        return [w for w in chw for _ in range(2)]
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None):
+        chw = channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+        return chw if self.absolute else self.expand_channel_weights(chw)
+
+    def _gradient(self, x, dtype):
+        """(N, C, H, W) -> (N, C, H, W) |grad| or (N, 2 C, H, W) components, in ``dtype``"""
+        from . import ops
+        N, Cc, H, W = x.shape
+        S = self.sht.analysis(x.float().contiguous())                               # (L, M, 2, N * Cp), rows (n, c)
+        Cp = S.shape[-1] // N
+        P = N * Cp
+        Rp = ops.round32(P)
+        if Rp != P:                                                                 # the vector kernel's rows come in 32s
+            S = torch.nn.functional.pad(S, (0, Rp - P))
+        g = self.ivsht.synthesis(S, P, t_zero=True).to(dtype)                       # (2, N * Cp, H, W)
+        g = g.view(2, N, Cp, H, W)[:, :, :Cc]
+        if self.absolute:
+            return g.pow(2).sum(dim=0).sqrt()
+        return g.permute(1, 2, 0, 3, 4).reshape(N, 2 * Cc, H, W)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        self._check(forecasts, observations, spatial_weights)
+        B, E, Cc, H, W = forecasts.shape
+        dtype = forecasts.dtype
+        with torch.autocast(device_type=forecasts.device.type, enabled=False):
+            f = self._gradient(forecasts.reshape(B * E, Cc, H, W), dtype)
+            o = self._gradient(observations, dtype)
+        Co = f.shape[1]
+        return self._score(f.reshape(B, E, Co, H, W).contiguous(), o.contiguous(), spatial_weights)
+
+
+class VortDivCRPSLoss(_EnsembleGridLoss):
+    """``VortDivCRPSLoss`` of ``makani/utils/losses/crps_loss.py:847-1019`` ("ensemble_vort_div_crps"): every (u, v) pair of the
+    channel list goes through the vector transform round trip (fp32, autocast off) and is scattered back, the other channels
+    pass through; the ensemble CRPS of the result, (B, C).  Analysis and synthesis are chained on the internal S layout (no
+    complex64 tensor in between).  Serial only."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, crps_type: str = "skillspread",
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
+                 ensemble_weights: Optional[torch.Tensor] = None, alpha: Optional[float] = 1.0, eps: Optional[float] = 1.0e-6,
+                 lmax: Optional[int] = None, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
+                         ensemble_distributed, ensemble_weights, alpha, eps)
+        from .sht import RealVectorSHT, InverseRealVectorSHT
+        self.register_buffer("wind_chans", torch.LongTensor(get_wind_channels(channel_names)), persistent=False)
+        self.vsht = RealVectorSHT(*img_shape, lmax=lmax, mmax=lmax, grid=grid_type)
+        self.isht = InverseRealVectorSHT(self.vsht.nlat, self.vsht.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+
+    @property
+    def n_channels(self):
+        return len(self.channel_names)
+
+    def average_wind_weights(self, chw):
+        wind = self.wind_chans.to(chw.device)
+        u, v = wind[0::2], wind[1::2]
+        avg = (chw[u] + chw[v]) / 2
+        chw[u] = avg
+        chw[v] = avg
+        return chw
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return self.average_wind_weights(channel_weighting(self.channel_names, channel_weight_type, time_diff_scale))
+
+    def _round_trip(self, x):
+        """(N, C, H, W) fp32 -> the same with the wind channels replaced by their transform round trip"""
+        Cw = self.wind_chans.shape[0]
+        if Cw == 0:
+            return x
+        N, Cc, H, W = x.shape
+        wind = x[:, self.wind_chans].reshape(N * (Cw // 2), 2, H, W)
+        xc = wind.transpose(0, 1).contiguous()                                      # (2, P, H, W): component outermost
+        S = self.vsht.analysis(xc)
+        back = self.isht.synthesis(S, xc.shape[1])                                  # (2, P, H, W)
+        back = back.transpose(0, 1).reshape(N, Cw, H, W)
+        return x.index_copy(1, self.wind_chans, back)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        self._check(forecasts, observations, spatial_weights)
+        B, E, Cc, H, W = forecasts.shape
+        with torch.autocast(device_type=forecasts.device.type, enabled=False):
+            f = self._round_trip(forecasts.float().reshape(B * E, Cc, H, W)).reshape(B, E, Cc, H, W)
+            o = self._round_trip(observations.float())
+        return self._score(f.contiguous(), o.contiguous(), spatial_weights)

@@ -595,9 +595,9 @@ def s_to_complex(S: torch.Tensor, B: int, Cc: int, l_off: int = 0, m_off: int = 
     return torch.view_as_complex(out)
 
 
-def complex_to_s(c: torch.Tensor) -> torch.Tensor:
+def complex_to_s(c: torch.Tensor, Cp: int = None) -> torch.Tensor:
     B, Cc, L, M = c.shape
-    Cp = round4(Cc)
+    Cp = round4(Cc) if Cp is None else Cp
     cr = torch.view_as_real(c.contiguous())
     S = torch.empty((L, M, 2, B * Cp), dtype=torch.float32, device=c.device)
     check(lib().mk_complex_to_slayout(ptr(cr), ptr(S), B, Cc, Cp, L, M, stream()), "complex_to_slayout")
@@ -845,6 +845,108 @@ class ComplexToSFn(torch.autograd.Function):
     def backward(ctx, gS):
         B, Cc, l_off, m_off = ctx.meta
         return s_to_complex(gS.contiguous(), B, Cc, l_off, m_off), None, None
+
+
+# --------------------------------------------------------------------------- #
+# Vector Legendre stage (csrc/vlegendre.hip).  A field of P (u, v) pairs is a scalar F / S tensor whose rows are
+# (component, pair) with Rp = P rounded up to 32 rows per component (``round32``): F (M, nlat, 2, 2 Rp), S (L, M, 2, 2 Rp) —
+# exactly what the FFT entry points and the complex <-> S conversions produce for a (2, P, ...) tensor with Cp = Rp.
+# --------------------------------------------------------------------------- #
+def round32(n: int) -> int:
+    return (n + 31) // 32 * 32
+
+
+class VectorMats:
+    """the two latitude functions of one vector transform in both orientations, as the kernel wants them:
+    ``nat`` = (W0, W1) each (M, L, kp) [synthesis-shaped launches], ``tr`` = (W0^T, W1^T) each (M, nlat, lp)
+    [analysis-shaped launches], ``band`` = (lo, hi) int32 device vectors of the common polar band or None"""
+
+    def __init__(self, nat, tr, band, L, nlat):
+        self.nat, self.tr, self.band, self.L, self.nlat = nat, tr, band, L, nlat
+
+
+def vector_legendre(X: torch.Tensor, vm: VectorMats, mode: int) -> torch.Tensor:
+    """mode 0: F (M, nlat, 2, 2 Rp) -> S (L, M, 2, 2 Rp);  1: S -> F;  2: F -> S (L, M, 2, Rp), spheroidal part only;
+    3: S (L, M, 2, Rp) -> F with a zero toroidal part (see include/makani_amd.h, mk_vlegendre)."""
+    gm = gemm_mode()
+    if gm == "fp32":
+        raise NotImplementedError("the vector Legendre kernels run on the split-bf16 engine (MAKANI_AMD_GEMM=auto, x6 or x3)")
+    limbs = 3 if gm == "x6" else 2
+    assert X.is_contiguous() and X.dtype == torch.float32
+    ana = mode in (0, 2)
+    if ana:
+        M, nlat, _, R = X.shape
+        Rp = R // 2
+        assert nlat == vm.nlat
+        out = torch.empty((vm.L, M, 2, Rp if mode == 2 else 2 * Rp), dtype=torch.float32, device=X.device)
+        m0, m1, rows, K = vm.tr[0], vm.tr[1], vm.L, nlat
+    else:
+        L, M, _, R = X.shape
+        Rp = R if mode == 3 else R // 2
+        assert L == vm.L
+        out = torch.empty((M, vm.nlat, 2, 2 * Rp), dtype=torch.float32, device=X.device)
+        m0, m1, rows, K = vm.nat[0], vm.nat[1], vm.nlat, L
+    assert m0.shape[0] == M and Rp % 32 == 0
+    p0, p1 = limb_planes(m0), limb_planes(m1)
+    lo, hi = vm.band if vm.band is not None else (None, None)
+    prods = 1 if mode == 3 else 2
+    with _timed(f"vlegendre_{'analysis' if ana else 'synthesis'}_k{vm.nlat}", flops=2.0 * prods * out.shape[-1] * 2 * vm.nlat * vm.L * M,
+                nbytes=4.0 * (X.numel() + out.numel() + 2 * M * vm.L * vm.nlat)):
+        check(lib().mk_vlegendre(ptr(p0), ptr(p1), p0.stride(0), p0.stride(1), p0.stride(2), limbs, ptr(X), ptr(out), mode,
+                                 rows, K, M, Rp, 0, ptr(lo), ptr(hi), stream()), "mk_vlegendre")
+    return out
+
+
+class VAnalysisFn(torch.autograd.Function):
+    """S = vector analysis of F (``s_only``: the spheroidal coefficients alone); backward = the synthesis-shaped launch with
+    the same (weighted) matrices"""
+
+    @staticmethod
+    def forward(ctx, F, vm, s_only=False):
+        ctx.vm, ctx.s_only = vm, s_only
+        return vector_legendre(F, vm, 2 if s_only else 0)
+
+    @staticmethod
+    def backward(ctx, gS):
+        return vector_legendre(gS.contiguous(), ctx.vm, 3 if ctx.s_only else 1), None, None
+
+
+class VSynthesisFn(torch.autograd.Function):
+    """F = vector synthesis of S (``t_zero``: S holds the spheroidal coefficients only, the toroidal ones are zero)"""
+
+    @staticmethod
+    def forward(ctx, S, vm, t_zero=False):
+        ctx.vm, ctx.t_zero = vm, t_zero
+        return vector_legendre(S, vm, 3 if t_zero else 1)
+
+    @staticmethod
+    def backward(ctx, gF):
+        return vector_legendre(gF.contiguous(), ctx.vm, 2 if ctx.t_zero else 0), None, None
+
+
+class VSToComplexFn(torch.autograd.Function):
+    """S (L, M, 2, B * Cp) -> complex64 (B, Cc, L, M) for any row padding Cp (the scalar pair's Cp is round4(Cc))"""
+
+    @staticmethod
+    def forward(ctx, S, B, Cc):
+        ctx.Cp = S.shape[3] // B
+        return s_to_complex(S, B, Cc)
+
+    @staticmethod
+    def backward(ctx, gc):
+        return complex_to_s(gc, ctx.Cp), None, None
+
+
+class VComplexToSFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, c, Cp):
+        ctx.meta = c.shape[:2]
+        return complex_to_s(c, Cp)
+
+    @staticmethod
+    def backward(ctx, gS):
+        B, Cc = ctx.meta
+        return s_to_complex(gS.contiguous(), B, Cc), None
 
 
 # --------------------------------------------------------------------------- #

@@ -121,3 +121,106 @@ class InverseRealSHT(_SHTBase):
         S = ops.ComplexToSFn.apply(c4)
         x = self.synthesis(S, c4.shape[0], c4.shape[1])
         return x.reshape(*lead, self.nlat, self.nlon)
+
+
+class _VectorSHTBase(_SHTBase):
+    """Shared by the vector pair: the two latitude functions of ``legendre.vector_legendre_matrices`` (convention, component
+    order and signs are written down there) as fp32 buffers in both orientations and their common polar band."""
+
+    def _register(self, W, name, name_t):
+        nat, tr = zip(*(self._padded(W[c]) for c in range(2)))
+        self.register_buffer(name, torch.stack(nat), persistent=False)         # (2, mmax, lmax, kp)
+        self.register_buffer(name_t, torch.stack(tr), persistent=False)        # (2, mmax, nlat, lp)
+        self._names = (name, name_t)
+        if ops.BAND_EPS > 0.0:
+            a = np.abs(W).max(axis=(0, 2))                                      # (mmax, nlat): largest entry per latitude
+            live = a > ops.BAND_EPS * np.maximum(a.max(axis=1, keepdims=True), 1e-300)
+            idx = np.arange(self.nlat)[None, :]
+            lo = np.where(live, idx, self.nlat).min(axis=1)
+            hi = np.where(live, idx + 1, 0).max(axis=1)
+            lo = np.minimum(lo, hi)
+            self.register_buffer("band_lo", torch.from_numpy(lo.astype(np.int32)), persistent=False)
+            self.register_buffer("band_hi", torch.from_numpy(hi.astype(np.int32)), persistent=False)
+        else:
+            self.band_lo = self.band_hi = None
+        self._vm = None
+
+    def _mats(self) -> "ops.VectorMats":
+        """the kernel's view of the buffers; rebuilt when the module has moved (the limb planes are cached per tensor object)"""
+        nat, tr = getattr(self, self._names[0]), getattr(self, self._names[1])
+        if self._vm is None or self._vm.key != (nat.data_ptr(), tr.data_ptr()):
+            band = (self.band_lo, self.band_hi) if self.band_lo is not None else None
+            self._vm = ops.VectorMats((nat[0], nat[1]), (tr[0], tr[1]), band, self.lmax, self.nlat)
+            self._vm.key = (nat.data_ptr(), tr.data_ptr())
+        return self._vm
+
+    @staticmethod
+    def _pairs_first(x, trailing):
+        """(..., 2, a, b) -> ((2, P, a, b) contiguous, lead shape): the component becomes the outer row index"""
+        if x.dim() < 3 or x.shape[-3] != 2:
+            raise ValueError(f"expected (..., 2, {trailing[0]}, {trailing[1]}), got {tuple(x.shape)}")
+        lead = x.shape[:-3]
+        return x.reshape(-1, 2, *x.shape[-2:]).transpose(0, 1).contiguous(), lead
+
+
+class RealVectorSHT(_VectorSHTBase):
+    """Forward vector transform, ``torch_harmonics.RealVectorSHT``'s interface: ``(..., 2, nlat, nlon)`` float32 | bfloat16 ->
+    ``(..., 2, lmax, mmax)`` complex64 (component 0 / 1 in: colatitudinal / azimuthal; out: spheroidal / toroidal).  Buffers
+    ``weights`` (2, mmax, lmax, kp) / ``weights_t`` (2, mmax, nlat, lp): the two latitude functions times the quadrature
+    weights.  Longitude FFT -> ONE vector Legendre launch (csrc/vlegendre.hip)."""
+
+    def __init__(self, nlat, nlon, lmax=None, mmax=None, grid="equiangular", norm="ortho", csphase=True):
+        super().__init__(nlat, nlon, lmax, mmax, grid, norm, csphase)
+        W = _leg.vector_legendre_matrices(self.mmax, self.lmax, self._theta, norm=norm, inverse=False, csphase=csphase)
+        self._register(W * self._wq[None, None, None, :], "weights", "weights_t")
+        c = 2.0 * math.pi / nlon
+        self._w = (c, c, c)
+
+    def analysis(self, xc: torch.Tensor, s_only: bool = False) -> torch.Tensor:
+        """(2, P, nlat, nlon) f32|bf16, component outermost -> S-layout (lmax, mmax, 2, 2 Rp), rows (coefficient kind, pair),
+        Rp = ``ops.round32(P)``; ``s_only``: (lmax, mmax, 2, Rp), the spheroidal coefficients alone."""
+        if xc.dim() != 4 or xc.shape[0] != 2 or xc.shape[-2] != self.nlat or xc.shape[-1] != self.nlon:
+            raise ValueError(f"expected (2, P, {self.nlat}, {self.nlon}), got {tuple(xc.shape)}")
+        F = ops.RfftFn.apply(xc, self.mmax, ops.round32(xc.shape[1]), self._w)
+        return ops.VAnalysisFn.apply(F, self._mats(), s_only)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"RealVectorSHT (HIP) supports float32 / bfloat16 input, got {x.dtype}")
+        if x.shape[-2] != self.nlat or x.shape[-1] != self.nlon:
+            raise ValueError(f"expected (..., 2, {self.nlat}, {self.nlon}), got {tuple(x.shape)}")
+        xc, lead = self._pairs_first(x, (self.nlat, self.nlon))
+        S = self.analysis(xc)
+        c = ops.VSToComplexFn.apply(S, 2, xc.shape[1])
+        return c.transpose(0, 1).reshape(*lead, 2, self.lmax, self.mmax)
+
+
+class InverseRealVectorSHT(_VectorSHTBase):
+    """Inverse vector transform: ``(..., 2, lmax, mmax)`` complex64 -> ``(..., 2, nlat, nlon)`` float32.  Buffers ``pct``
+    (2, mmax, lmax, kp) / ``pct_t`` (2, mmax, nlat, lp)."""
+
+    def __init__(self, nlat, nlon, lmax=None, mmax=None, grid="equiangular", norm="ortho", csphase=True):
+        super().__init__(nlat, nlon, lmax, mmax, grid, norm, csphase)
+        W = _leg.vector_legendre_matrices(self.mmax, self.lmax, self._theta, norm=norm, inverse=True, csphase=csphase)
+        self._register(W, "pct", "pct_t")
+        self._w = (1.0, 2.0, 1.0)
+
+    def synthesis(self, S: torch.Tensor, P: int, out_dtype=torch.float32, t_zero: bool = False) -> torch.Tensor:
+        """S-layout (lmax, mmax, 2, 2 Rp) -> (2, P, nlat, nlon), component outermost.  ``t_zero``: S is (lmax, mmax, 2, Rp), the
+        spheroidal coefficients of P fields whose toroidal part is zero (a gradient) — nothing is stored or multiplied for it."""
+        F = ops.VSynthesisFn.apply(S, self._mats(), t_zero)
+        return ops.IrfftFn.apply(F, 2, P, self.nlon, out_dtype, self._w)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, c: torch.Tensor) -> torch.Tensor:
+        if c.dtype != torch.complex64:
+            raise TypeError(f"InverseRealVectorSHT (HIP) supports complex64 input, got {c.dtype}")
+        if c.shape[-2] != self.lmax or c.shape[-1] != self.mmax:
+            raise ValueError(f"expected (..., 2, {self.lmax}, {self.mmax}), got {tuple(c.shape)}")
+        cc, lead = self._pairs_first(c, (self.lmax, self.mmax))
+        S = ops.VComplexToSFn.apply(cc, ops.round32(cc.shape[1]))
+        x = self.synthesis(S, cc.shape[1])
+        return x.transpose(0, 1).reshape(*lead, 2, self.nlat, self.nlon)

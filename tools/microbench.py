@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -261,6 +261,29 @@ def sht():
             ms = timeit(lambda: ops.rfft_rows(x, mmax, R, (c, c, c)), reps=10, warm=2)
             print(f"   rfft 1440 fp32 C=73 full spectrum : {ms:7.3f} ms")
         del S, x
+
+
+def vsht():
+    """vector Legendre stage (csrc/vlegendre.hip) for P pairs beside the SCALAR Legendre launch on 2 P planes (same F / S
+    bytes, half the matrix bytes, half the MFMA work), same process, full band L = M = nlat; ratio = vector / scalar"""
+    for nlat, nlon, grid, P in ((721, 1440, "equiangular", 64), (360, 720, "equiangular", 64)):
+        L = M = nlat
+        V = ma.RealVectorSHT(nlat, nlon, lmax=L, mmax=M, grid=grid).to(dev)
+        IV = ma.InverseRealVectorSHT(nlat, nlon, lmax=L, mmax=M, grid=grid).to(dev)
+        S = ma.RealSHT(nlat, nlon, lmax=L, mmax=M, grid=grid).to(dev)
+        I = ma.InverseRealSHT(nlat, nlon, lmax=L, mmax=M, grid=grid).to(dev)
+        Rp = ops.round32(P)
+        F = torch.randn(M, nlat, 2, 2 * Rp, device=dev)
+        Sc = torch.randn(L, M, 2, 2 * Rp, device=dev)
+        for name, vec, sca in (("analysis ", lambda: ops.vector_legendre(F, V._mats(), 0), lambda: ops.legendre_analysis(F, S.weights_t, L)),
+                               ("synthesis", lambda: ops.vector_legendre(Sc, IV._mats(), 1), lambda: ops.legendre_synthesis(Sc, I.pct, nlat))):
+            ts = timeit(sca, reps=20, warm=3)
+            tv = timeit(vec, reps=20, warm=3)
+            ts2 = timeit(sca, reps=20, warm=3)                  # the scalar launch again: drift of the box within the run
+            print(f"vsht {name} {nlat}x{nlon} L=M={L} P={P}: vector {tv:7.3f} ms  scalar(2P planes) {ts:7.3f} / {ts2:7.3f} ms  ratio {tv / min(ts, ts2):5.2f}")
+        tz = timeit(lambda: ops.vector_legendre(Sc[..., :Rp].contiguous(), IV._mats(), 3), reps=20, warm=3)
+        print(f"vsht synthesis t=0 {nlat}x{nlon} P={P}: {tz:7.3f} ms (includes one S copy)")
+        del V, IV, S, I, F, Sc
 
 
 if __name__ == "__main__":
