@@ -404,6 +404,26 @@ int mk_crps(const void* f, int f_dtype, const void* obs, int o_dtype, const floa
 int mk_crps_complex(const void* f, const void* obs, const float* q, const float* w, const float* gout, float* partial, void* gf,
                     int B, int E, int C, long long hw, float alpha, int grad, void* stream);
 
+/* ---- ensemble energy scores (grid Lp, Sobolev, per-degree spectral L2) ------------------------------------------------
+ * Replace the pair tensors of makani/utils/losses/energy_score.py:30-652 (LpEnergyScoreLoss, SobolevEnergyScoreLoss,
+ * SpectralL2EnergyScoreLoss) and their autograd; three stages (makani_amd/csrc/escore.hip).
+ * f: (B, E, C, N) members, kind MK_F32 | MK_BF16 | 2 = complex64 (re, im interleaved; p = 2); obs: (B, C, N) f32 (complex64
+ * for kind 2); q: (N) weights; w: optional (B, C, N) f32.  The plane of N points is S segments of N / S points (S = 1, or one
+ * per degree of an (L, M) plane).  K = E + E (E - 1) / 2 sums per segment: E skills, then the pairs i < j in lexicographic
+ * order.  nanmode 0: a NaN observation masks the point, a NaN member counts as 0; 1: a NaN observation or member masks it.
+ * 1 <= E <= 32, p >= 1.
+ * mk_escore_sums:   sums (B, C, S, K) f32; ws: mk_escore_sums_workspace(...) floats of scratch (NULL when that is 0).
+ * mk_escore_finish: sums -> loss (B, Cout) and table (B, Cout, S, K) = d loss / d sums (0 where a sum is below eps);
+ *                   Cout = reduce ? 1 : C (channels summed in order); scale: optional (nscale = 1 | Cout) spread factors.
+ * mk_escore_grad:   gf (shape / dtype of f) = gout[b][co] * q * w * sum_k table[b][co][s][k] d term_k / d f_e; 0 where masked. */
+long long mk_escore_sums_workspace(int B, int E, int C, long long N, int S, int nanmode);
+int mk_escore_sums(const void* f, int kind, const void* obs, const float* q, const float* w, float* sums, float* ws, int B, int E,
+                   int C, long long N, int S, int nanmode, float p, void* stream);
+int mk_escore_finish(const float* sums, const float* scale, int nscale, float* loss, float* table, int B, int E, int C, int S,
+                     int reduce, float p, float beta, float alpha, float eps, void* stream);
+int mk_escore_grad(const void* f, int kind, const void* obs, const float* q, const float* w, const float* table, const float* gout,
+                   void* gf, int B, int E, int C, int Cout, long long N, int S, int nanmode, float p, void* stream);
+
 /* ---- DISCO convolution and S2 resampling (FourCastNet3's local operators) ----------------------------------------
  * Replace th.DiscreteContinuousConvS2's sparse contraction and th.ResampleS2 [torch-harmonics, un-vendored; call sites
  * makani/models/networks/fourcastnet3.py:189-205 (encoder), :356-381 (decoder), :518-534 (local blocks)].

@@ -861,3 +861,260 @@ class VortDivCRPSLoss(_EnsembleGridLoss):
             f = self._round_trip(forecasts.float().reshape(B * E, Cc, H, W)).reshape(B, E, Cc, H, W)
             o = self._round_trip(observations.float())
         return self._score(f.contiguous(), o.contiguous(), spatial_weights)
+
+
+# --------------------------------------------------------------------------- #
+# ensemble energy scores (makani/utils/losses/energy_score.py:30-652)
+# --------------------------------------------------------------------------- #
+_ES_COMPLEX = 2            # `kind` of mk_escore_*: complex64 members (MK_F32 / MK_BF16 otherwise)
+
+
+class EnergyScoreFn(torch.autograd.Function):
+    """The three stages of ``csrc/escore.hip``.  forecasts (B, E, C, N) f32 | bf16 | complex64 in that layout, obs (B, C, N),
+    q (N), wgt optional (B, C, N); the plane of N points is ``nseg`` segments.  ``mk_escore_sums`` -> sums (B, C, nseg, K);
+    the sums are added over ``sum_groups`` (process groups: the all-reduces of the parallel variants fall BEFORE the root);
+    ``mk_escore_finish`` -> loss (B, C_out) and the table d loss / d sums, kept for ``mk_escore_grad``.  Gradient with
+    respect to the forecasts only (the backward of a SUM all-reduce is the identity)."""
+
+    @staticmethod
+    def forward(ctx, forecasts, obs, q, wgt, scale, nseg, nanmode, reduce, p, beta, alpha, eps, sum_groups):
+        B, E, Cc, N = forecasts.shape
+        if forecasts.is_complex():
+            kind = _ES_COMPLEX
+            f = torch.view_as_real(forecasts.to(torch.complex64).contiguous())
+            o = torch.view_as_real(obs.to(torch.complex64).contiguous())
+        else:
+            f = _prep(forecasts)
+            kind = dtype_code(f)
+            o = obs.float().contiguous()
+        q = q.float().contiguous()
+        w = wgt.float().contiguous() if wgt is not None else None
+        K = E + E * (E - 1) // 2
+        sums = torch.empty((B, Cc, nseg, K), dtype=torch.float32, device=f.device)
+        nws = lib().mk_escore_sums_workspace(B, E, Cc, N, nseg, nanmode)
+        ws = torch.empty((nws,), dtype=torch.float32, device=f.device) if nws else None
+        check(lib().mk_escore_sums(ptr(f), kind, ptr(o), ptr(q), ptr(w), ptr(sums), ptr(ws), B, E, Cc, N, nseg, nanmode, float(p),
+                                   stream()), "mk_escore_sums")
+        from . import ops
+        for group in sum_groups:
+            ops._all_reduce_sum(sums, group)
+        Cout = 1 if reduce else Cc
+        loss = torch.empty((B, Cout), dtype=torch.float32, device=f.device)
+        table = torch.empty((B, Cout, nseg, K), dtype=torch.float32, device=f.device)
+        sc = scale.float().contiguous() if scale is not None else None
+        check(lib().mk_escore_finish(ptr(sums), ptr(sc), sc.numel() if sc is not None else 0, ptr(loss), ptr(table), B, E, Cc, nseg,
+                                     int(reduce), float(p), float(beta), float(alpha), float(eps), stream()), "mk_escore_finish")
+        ctx.save_for_backward(f, o, q, w if w is not None else torch.empty(0, device=f.device), table)
+        ctx.meta = (kind, w is not None, nseg, nanmode, float(p), forecasts.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        f, o, q, w, table = ctx.saved_tensors
+        kind, has_w, nseg, nanmode, p, dt = ctx.meta
+        B, E, Cc, N = f.shape[:4]
+        gf = torch.empty_like(f)
+        go = g.float().contiguous()
+        check(lib().mk_escore_grad(ptr(f), kind, ptr(o), ptr(q), ptr(w) if has_w else None, ptr(table), ptr(go), ptr(gf), B, E, Cc,
+                                   table.shape[1], N, nseg, nanmode, p, stream()), "mk_escore_grad")
+        gf = torch.view_as_complex(gf) if kind == _ES_COMPLEX else gf.to(dt)
+        return (gf,) + (None,) * 12
+
+
+def _escore_checks(forecasts, ensemble_weights):
+    if forecasts.dim() != 5:
+        raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
+    if ensemble_weights is not None:
+        raise NotImplementedError("currently only constant ensemble weights are supported")
+
+
+def _escore_size_check(E):
+    if E > MAX_ENSEMBLE:
+        raise NotImplementedError(f"ensemble size {E}: the HIP energy-score kernels are built for 1 <= E <= {MAX_ENSEMBLE}")
+
+
+class _EnergyScoreMixin:
+    """what the three energy-score classes share with the reference's: the loss type, the channel count and weighting"""
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
+    @property
+    def n_channels(self):
+        return 1 if self.channel_reduction else len(self.channel_names)
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: str = None) -> torch.Tensor:
+        if self.channel_reduction:
+            return torch.ones(1)
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+
+class LpEnergyScoreLoss(_EnergyScoreMixin, nn.Module):
+    """``LpEnergyScoreLoss`` of ``makani/utils/losses/energy_score.py:30-250`` ("lp_energy_score"; "l2_energy_score" is the
+    alias ``L2EnergyScoreLoss``): mean_e ||o - f_e||^beta - (E - 1 + alpha) / (E^2 (E - 1)) sum_{i<j} ||f_i - f_j||^beta with
+    the quadrature-weighted Lebesgue norm ||x|| = (sum_n q w |x_n|^p)^(1/p) over the grid, per channel or (``channel_reduction``)
+    over all channels.  ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W), spatial_weights=None,
+    lead_time_step=None) -> (B, C) | (B, 1)``.  The members are read in place, once for E <= 8 (``csrc/escore.hip``); no pair
+    tensor exists.  1 <= E <= 32 (more: NotImplementedError).
+
+    Deviation, stated: ``p < 1`` raises NotImplementedError — the reference's autograd yields NaN gradients at coincident
+    members there (|d|^(p - 1) at d = 0)."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
+                 channel_reduction: Optional[bool] = True, alpha: Optional[float] = 1.0, beta: Optional[float] = 1.0,
+                 p: Optional[float] = 2.0, eps: Optional[float] = 1.0e-6, spread_temper_steps: Optional[int] = 0, **kwargs):
+        super().__init__()
+        if float(p) < 1.0:
+            raise NotImplementedError(f"p = {p}: the energy score is built for p >= 1 (the gradient of |d|^p is unbounded at "
+                                      "coincident members for p < 1)")
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
+        self.spatial_distributed = self.quadrature.distributed
+        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.channel_reduction, self.alpha, self.beta, self.p, self.eps = channel_reduction, alpha, beta, float(p), eps
+        self.spread_temper_steps = spread_temper_steps
+        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
+        self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                lead_time_step: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        _escore_checks(forecasts, self.ensemble_weights)
+        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
+            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
+                             f"observations (found {observations.dim()}).")
+        if not forecasts.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        B, E, Cc, H, W = forecasts.shape
+        f = forecasts.reshape(B, E, Cc, H * W)
+        o = observations.reshape(B, Cc, H * W)
+        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
+        q = self.quad_weight_split.reshape(-1)
+        groups = []
+        if self.ensemble_distributed:               # members <-> a share of the points (:139-151), the sums added over the group (:188-190)
+            f, o, q, w, group = _ensemble_split(f, o, q, w)
+            groups.append(group)
+        if self.spatial_distributed:
+            from . import distributed as thd
+            groups.append(thd.spatial_group())
+        _escore_size_check(f.shape[1])
+        scale = None
+        if self.training and self.spread_temper_steps > 0 and lead_time_step is not None:       # :243-245
+            scale = torch.clamp(lead_time_step.float().to(f.device) / self.spread_temper_steps, min=1.0).reshape(-1)
+            if scale.numel() not in (1, self.n_channels):
+                raise ValueError(f"lead_time_step holds {scale.numel()} entries for {self.n_channels} output channels")
+        return EnergyScoreFn.apply(f, o, q, w, scale, 1, 0, self.channel_reduction, self.p, self.beta, self.alpha, self.eps, groups)
+
+
+L2EnergyScoreLoss = LpEnergyScoreLoss          # backward-compatibility alias, as the reference's
+
+
+class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
+    """the spectral energy scores: HIP ``RealSHT`` of members and observation (fp32, autocast off, / sqrt(4 pi)), then the
+    kernels of ``csrc/escore.hip`` on the complex coefficients (squared modulus; a coefficient where the observation or any
+    member is NaN is masked)"""
+
+    def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                 ensemble_distributed, ensemble_weights, channel_reduction, alpha, beta, eps):
+        SpectralLpLoss.__init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type,
+                                spatial_distributed=spatial_distributed, lmax=lmax, eps=eps)
+        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.channel_reduction, self.alpha, self.beta = channel_reduction, alpha, beta
+        self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
+
+    def _coefficients(self, forecasts, observations):
+        _escore_checks(forecasts, self.ensemble_weights)
+        if not forecasts.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        with torch.autocast(device_type=forecasts.device.type, enabled=False):
+            f = self.sht(forecasts.float()) / math.sqrt(4.0 * math.pi)
+            o = self.sht(observations.float()) / math.sqrt(4.0 * math.pi)
+        return f, o
+
+    def _ensemble_split_lm(self, f, o, q):
+        """f (B, E_loc, C, L, M) complex, o (B, C, L, M), q (L, M): the members of the group on this rank's share of the
+        orders m (the reference's ``distributed_transpose(..., (-1, 0))`` of the last axis).  The exchange moves real tensors:
+        (re, im) travel as two rows of the channel axis."""
+        B, E, Cc, L, M = f.shape
+        fr = torch.view_as_real(f.contiguous()).permute(0, 1, 2, 3, 5, 4).reshape(B, E, Cc * L * 2, M)
+        fr, os_, qs, _, group = _ensemble_split(fr, o, q, None)
+        Ml = fr.shape[-1]
+        fs = torch.view_as_complex(fr.reshape(B, -1, Cc, L, 2, Ml).permute(0, 1, 2, 3, 5, 4).contiguous())
+        return fs, os_, qs, group
+
+    def _score(self, forecasts, observations, per_degree):
+        from . import comm as _comm
+        f, o = self._coefficients(forecasts, observations)
+        q = self.lm_weights
+        groups = []
+        if self.ensemble_distributed:
+            f, o, q, group = self._ensemble_split_lm(f, o, q)
+            groups.append(group)
+        if self.spatial_distributed:                # per degree: the orders are summed over "w", the degrees (below) over "h"
+            from . import distributed as thd
+            if not per_degree:
+                groups.append(thd.spatial_group())
+            elif _comm.get_size("w") > 1:
+                groups.append(_comm.get_group("w"))
+        B, E, Cc, L, M = f.shape
+        _escore_size_check(E)
+        loss = EnergyScoreFn.apply(f.reshape(B, E, Cc, L * M), o.reshape(B, Cc, L * M), q.reshape(-1), None, None,
+                                   L if per_degree else 1, 1, self.channel_reduction, 2.0, self.beta, self.alpha, self.eps, groups)
+        if per_degree and self.spatial_distributed and _comm.get_size("h") > 1:
+            loss = _ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+        return loss
+
+
+class SobolevEnergyScoreLoss(_SpectralEnergyScore):
+    """``SobolevEnergyScoreLoss`` of ``makani/utils/losses/energy_score.py:257-460`` ("sobolev_energy_score"): the energy score
+    in the Sobolev norm ||x||^2 = sum_{l,m} (offset + relative_weight l (l + 1))^fraction w(m) |x_lm|^2 (w(0) = 1, w(m > 0) = 2)
+    of the spherical-harmonic coefficients, per channel or over all channels.  ``forward(forecasts (B, E, C, H, W),
+    observations (B, C, H, W)) -> (B, C) | (B, 1)``."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
+                 channel_reduction: Optional[bool] = True, alpha: Optional[float] = 1.0, beta: Optional[float] = 1.0,
+                 offset: Optional[float] = 1.0, fraction: Optional[float] = 1.0, relative_weight: Optional[float] = 1.0,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, ensemble_weights, channel_reduction, alpha, beta, eps)
+        self.fraction, self.offset, self.relative_weight = fraction, offset, relative_weight
+        l = torch.arange(self.sht.lmax, dtype=torch.float32)
+        m_weights = 2 * torch.ones(self.sht.mmax, dtype=torch.float32)
+        m_weights[0] = 1.0
+        lm = (offset + relative_weight * l * (l + 1)).pow(fraction)[:, None] * m_weights[None, :]                 # :308-315
+        Ll, Ml = self.lm_weights.shape
+        self.register_buffer("lm_weights", lm[self._l_off:self._l_off + Ll, self._m_off:self._m_off + Ml].contiguous(), persistent=False)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        return self._score(forecasts, observations, per_degree=False)
+
+
+class SpectralL2EnergyScoreLoss(_SpectralEnergyScore):
+    """``SpectralL2EnergyScoreLoss`` of ``makani/utils/losses/energy_score.py:463-652`` ("spectral_l2_energy_score"): one L2
+    energy score per degree l (the norm sums the Parseval-weighted |x_lm|^2 over the orders m), summed over the degrees.
+    ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W)) -> (B, C) | (B, 1)``."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
+                 channel_reduction: Optional[bool] = True, alpha: Optional[float] = 1.0, beta: Optional[float] = 1.0,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, ensemble_weights, channel_reduction, alpha, beta, eps)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        return self._score(forecasts, observations, per_degree=True)

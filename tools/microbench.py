@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -284,6 +284,57 @@ def vsht():
         tz = timeit(lambda: ops.vector_legendre(Sc[..., :Rp].contiguous(), IV._mats(), 3), reps=20, warm=3)
         print(f"vsht synthesis t=0 {nlat}x{nlon} P={P}: {tz:7.3f} ms (includes one S copy)")
         del V, IV, S, I, F, Sc
+
+
+def escore():
+    """energy-score stages 1 (mk_escore_sums) and 3 (mk_escore_grad) at 721 x 1440, C = 73, B = 1 as a fraction of HBM peak on
+    ALGORITHMIC traffic — (E + 1) plane reads forward, (E + 1) reads + E writes backward — beside crps_kernel at the same shape
+    and, for E = 2 only (its pair tensor grows with E^2), a torch restatement of the reference formula"""
+    from makani_amd import _lib
+    from makani_amd._lib import lib, ptr, stream, check
+    PEAK = 8.0e12
+    H, W, C, B = 721, 1440, 73, 1
+    N = H * W
+    q = torch.rand(N, device=dev) / N
+    for E in (2, 8, 16):
+        for dt in (torch.float32, torch.bfloat16):
+            f = torch.randn(B, E, C, N, device=dev).to(dt)
+            o = torch.randn(B, C, N, device=dev)
+            kind = _lib.dtype_code(f)
+            K = E + E * (E - 1) // 2
+            sums = torch.empty(B, C, 1, K, device=dev)
+            ws = torch.empty(lib().mk_escore_sums_workspace(B, E, C, N, 1, 0), device=dev)
+            loss, table = torch.empty(B, 1, device=dev), torch.empty(B, 1, 1, K, device=dev)
+            gout, gf = torch.ones(B, 1, device=dev), torch.empty_like(f)
+
+            def fwd():
+                check(lib().mk_escore_sums(ptr(f), kind, ptr(o), ptr(q), None, ptr(sums), ptr(ws), B, E, C, N, 1, 0, 2.0, stream()))
+
+            def bwd():
+                check(lib().mk_escore_grad(ptr(f), kind, ptr(o), ptr(q), None, ptr(table), ptr(gout), ptr(gf), B, E, C, 1, N, 1, 0, 2.0, stream()))
+
+            fwd()
+            check(lib().mk_escore_finish(ptr(sums), None, 0, ptr(loss), ptr(table), B, E, C, 1, 1, 2.0, 1.0, 1.0, 1e-6, stream()))
+            es = f.element_size()
+            bytes_f = C * N * (E * es + 4)
+            bytes_b = C * N * (E * es + 4 + E * es)
+            tf, tb = timeit(fwd, reps=10, warm=2), timeit(bwd, reps=10, warm=2)
+            crps = ma.CRPSLoss(img_shape=(H, W), crop_shape=(H, W), crop_offset=(0, 0), channel_names=[str(c) for c in range(C)],
+                               grid_type="equiangular").to(dev)
+            f5, o4 = f.view(B, E, C, H, W), o.view(B, C, H, W)
+            tc = timeit(lambda: crps(f5, o4), reps=10, warm=2)
+            pct = lambda nbytes, ms: nbytes / (ms * 1e-3) / PEAK * 100
+            line = (f"escore E={E:2d} {str(dt)[6:]:9s} sums {tf:7.3f} ms {pct(bytes_f, tf):5.1f} % of peak | "
+                    f"grad {tb:7.3f} ms {pct(bytes_b, tb):5.1f} % | crps fwd {tc:7.3f} ms {pct(bytes_f, tc):5.1f} %")
+            if E == 2 and dt == torch.float32:
+                def torch_ref():
+                    fe = torch.moveaxis(f, 1, 0)
+                    d = ((fe[0] - fe[1]).abs().pow(2.0) * q).sum(-1).sum(-1, keepdim=True)
+                    s = ((o.unsqueeze(0) - fe).abs().pow(2.0) * q).sum(-1).sum(-1, keepdim=True)
+                    return s.sqrt().sum(0) / E - 0.5 * d.sqrt() * 2.0 * E / (E * E * (E - 1))
+                line += f" | torch formula fwd {timeit(torch_ref, reps=5, warm=1):7.3f} ms"
+            print(line, flush=True)
+            del f, o, gf
 
 
 if __name__ == "__main__":
