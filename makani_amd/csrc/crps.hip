@@ -54,19 +54,25 @@ __device__ __forceinline__ float crps_point(float (&f)[EM], int E, float obs, in
     float score;
     float g[EM];
     if (type == CRPS_GAUSS) {
-        float mu = 0.f;
+        // everything relative to the first member: f_e - f_0 is exact for close members, so the deviations from the mean keep
+        // their relative accuracy.  f_e - mean(f) directly carries the rounding of the mean (half an ulp of |f|); with two
+        // members 1e-3 apart around 10 that is 1e-3 of the deviation, and of the gradient's (f_e - mu) / sigma term
+        const float piv = f[0];
+        float md = 0.f;                // mu - piv
 #pragma unroll
         for (int e = 0; e < EM; ++e)
-            if (e < E) mu += f[e];
-        mu *= inv_e;
+            if (e < E) md += f[e] - piv;
+        md *= inv_e;
         float var = 0.f;
 #pragma unroll
-        for (int e = 0; e < EM; ++e)
-            if (e < E) var += (f[e] - mu) * (f[e] - mu);
+        for (int e = 0; e < EM; ++e) {
+            f[e] = (f[e] - piv) - md;  // from here on f holds the deviations
+            if (e < E) var += f[e] * f[e];
+        }
         var *= inv_e;
         const float sraw = sqrtf(var);
         const float sigma = fmaxf(sraw, eps);
-        const float z = (obs - mu) / sigma;
+        const float z = ((obs - piv) - md) / sigma;
         const float pdf = 0.3989422804014327f * __expf(-0.5f * z * z);
         const float cdf2m1 = erff(z * 0.7071067811865476f);
         score = sigma * (z * cdf2m1 + 2.f * pdf - 0.5641895835477563f);
@@ -74,7 +80,7 @@ __device__ __forceinline__ float crps_point(float (&f)[EM], int E, float obs, in
             const float dmu = -cdf2m1, dsig = 2.f * pdf - 0.5641895835477563f;
 #pragma unroll
             for (int e = 0; e < EM; ++e)
-                g[e] = dmu * inv_e + ((sraw > eps) ? dsig * (f[e] - mu) * inv_e / sigma : 0.f);
+                g[e] = dmu * inv_e + ((sraw > eps) ? dsig * f[e] * inv_e / sigma : 0.f);
         }
     } else {
         // ordinal ranks 1..E: members smaller than f_e, plus equal members that come before e
@@ -331,7 +337,8 @@ extern "C" int mk_crps(const void* f, int f_dtype, const void* obs, int o_dtype,
     MK_REQUIRE(type >= 0 && type <= 4, "crps: unknown score type %d", type);
     MK_REQUIRE(!ens_w || type == CRPS_CDF, "crps: ensemble weights are defined for the cdf form only");
     MK_REQUIRE(grad ? (gout && gf) : (partial != nullptr), "crps: missing output");
-    MK_REQUIRE((long long)B * C <= 65535, "crps: too many planes");
+    MK_REQUIRE((long long)B * C <= 65535, "crps: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
+               (long long)B * C);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)mk_crps_chunks(hw), (unsigned)(B * C));
 #define MK_CRPS_GO(TF, TO)                                                                                                          \
@@ -352,7 +359,8 @@ extern "C" int mk_crps_complex(const void* f, const void* obs, const float* q, c
                                void* gf, int B, int E, int C, long long hw, float alpha, int grad, void* stream) {
     MK_REQUIRE(f && obs && q && B > 0 && E >= 2 && E <= MAXE && C > 0 && hw > 0, "crps_complex: bad arguments (2 <= E <= 32)");
     MK_REQUIRE(grad ? (gout && gf) : (partial != nullptr), "crps_complex: missing output");
-    MK_REQUIRE((long long)B * C <= 65535, "crps_complex: too many planes");
+    MK_REQUIRE((long long)B * C <= 65535, "crps_complex: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
+               (long long)B * C);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)mk_crps_chunks(hw), (unsigned)(B * C));
 #define MK_CX(N)                                                                                                                     \

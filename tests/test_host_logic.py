@@ -512,6 +512,15 @@ def test_c_abi_host_side_planning_functions():
     assert L.mk_conv1x1_wgrad_workspace(384, 384, 1, 1038240) % (384 * (384 + 1)) == 0
 
 
+def test_crps_chunk_counts():
+    """mk_crps_chunks: one chunk per 1 024 points, capped at 64.  The planes of tests/test_gpu_crps.py reach the paths they are
+    named for: 40 points one chunk, 16 380 sixteen, 65 702 the cap with a fifth stride for some threads (64 x 256 x 4 = 65 536);
+    the 721 x 1440 training plane runs at the cap"""
+    from makani_amd._lib import lib
+    assert [lib().mk_crps_chunks(hw) for hw in (1, 1024, 1025, 16380, 65536, 65702, 1038240)] == [1, 1, 2, 16, 64, 64, 64]
+    assert lib().mk_crps_chunks(40) == 1 and lib().mk_crps_chunks(37 * 72) == 3 and lib().mk_crps_chunks(33 * 40) == 2
+
+
 def test_channel_gemm_kernel_choice_for_the_shapes_of_the_networks(tmp_path):
     """csrc/conv1x1_plan.h (plain C++, compiled here for the host): the kernel mk_conv1x1_nn launches for every channel GEMM
     of the networks — full grids and the shards of one rank — with each epilogue, and under the two overrides"""
