@@ -424,6 +424,24 @@ int mk_escore_finish(const float* sums, const float* scale, int nscale, float* l
 int mk_escore_grad(const void* f, int kind, const void* obs, const float* q, const float* w, const float* table, const float* gout,
                    void* gf, int B, int E, int C, int Cout, long long N, int S, int nanmode, float p, void* stream);
 
+/* ---- spectral noise processes on the sphere (makani/models/noise.py: BaseNoiseS2 / DiffusionNoiseS2 / DummyNoiseS2 update) ----
+ * state: (B, T, C, L, M, 2) f32, updated in place in one pass (makani_amd/csrc/noise.hip).  s = reflect ? -1 : 1.
+ *   MK_NOISE_WHITE:   state[:, t] = s xi[t]                                                     (T levels drawn)
+ *   MK_NOISE_AR:      levels 1 .. T-1 move to 0 .. T-2; new last = phi[c] old last + s sigma[c][l] xi          (1 level drawn)
+ *   MK_NOISE_REPLACE: eta[t] = s sigma[c][l] xi[t]; new[0] = eta[0] / sqrt(1 - phi[c]^2); new[t] = phi[c] new[t-1] + eta[t]   (T levels)
+ * sigma (C, L), phi (C) f32 (unused, may be NULL, for MK_NOISE_WHITE).
+ * xi = NULL: standard normals from Philox4x32-10 + Box-Muller; rng = device int64 {seed, offset}, key = seed, counter =
+ *   (g, offset + t) with g the index of a group of four consecutive elements of level t flattened as (B, C, L, M, 2).  The
+ *   kernel only reads rng: enqueue mk_noise_advance(rng, levels drawn) behind it.
+ * xi != NULL: the innovations are read from xi, (B, 1, C, L, M, 2) for MK_NOISE_AR and (B, T, C, L, M, 2) otherwise; rng is not read.
+ * C L M 2 < 2^31.  16-byte accesses when C L M 2 is a multiple of 4 and the pointers are 16-byte aligned, scalar ones otherwise. */
+#define MK_NOISE_WHITE 0
+#define MK_NOISE_AR 1
+#define MK_NOISE_REPLACE 2
+int mk_noise_update(float* state, const float* xi, const float* sigma, const float* phi, const long long* rng, int mode, int B,
+                    int T, int C, int L, int M, int reflect, void* stream);
+int mk_noise_advance(long long* rng, long long n, void* stream);
+
 /* ---- DISCO convolution and S2 resampling (FourCastNet3's local operators) ----------------------------------------
  * Replace th.DiscreteContinuousConvS2's sparse contraction and th.ResampleS2 [torch-harmonics, un-vendored; call sites
  * makani/models/networks/fourcastnet3.py:189-205 (encoder), :356-381 (decoder), :518-534 (local blocks)].

@@ -10,9 +10,12 @@ from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss
 from .stepper import MultiStepWrapper, SingleStepWrapper
 from .disco import DiscreteContinuousConvS2, ResampleS2
 from .fcn3 import AtmoSphericNeuralOperatorNet
+from .noise import BaseNoiseS2, IsotropicGaussianRandomFieldS2, DiffusionNoiseS2, DummyNoiseS2, InputNoise, build_noise, noise_seed_reflect
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
            "SphericalFourierNeuralOperatorNet", "NeuralOperatorBlock", "SpectralFilterLayer", "GeometricLpLoss",
            "GridQuadrature", "SpectralLpLoss", "SpectralH1Loss", "CRPSLoss", "SpectralCRPSLoss", "GeometricInstanceNormS2", "MultiStepWrapper", "SingleStepWrapper",
            "DiscreteContinuousConvS2", "ResampleS2", "AtmoSphericNeuralOperatorNet",
-           "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss"]
+           "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
+           "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
+           "noise_seed_reflect"]

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -335,6 +335,40 @@ def escore():
                 line += f" | torch formula fwd {timeit(torch_ref, reps=5, warm=1):7.3f} ms"
             print(line, flush=True)
             del f, o, gf
+
+
+def noise():
+    """the diffusion noise's autoregressive update (mk_noise_update + mk_noise_advance) at the FourCastNet3 recipe's size, beside
+    the reference's torch formulation of the same update on GPU tensors and a plain device copy of the state as the bandwidth
+    yardstick; traffic counted as one read and one write of the state.  Three rounds, the three timed in turn within each; then
+    the inverse SHT's share of update + forward."""
+    T, C, nlat, nlon = 1, 8, 721, 1440
+    for B in (16, 2):
+        m = ma.DiffusionNoiseS2((nlat, nlon), B, C, num_time_steps=T, kT=[0.5 * (100.0 * 2 ** c / 6370.0) ** 2 for c in range(C)]).to(dev)
+        m.update(replace_state=True)
+        st = m.state
+        nbytes = 2 * st.numel() * 4
+        twin, dst = st.clone(), torch.empty_like(st)
+        gen = torch.Generator(device=dev).manual_seed(333)
+
+        def torch_update():                                   # normal_, scale, damp + add, copy_: the reference's operations
+            xi = torch.empty_like(twin).normal_(mean=0.0, std=1.0, generator=gen)
+            eta = m.sigma_l * xi
+            twin.copy_(m.phi * twin + eta)
+
+        for rnd in range(3):
+            tk = timeit(m.update, reps=50, warm=3)
+            tt = timeit(torch_update, reps=20, warm=2)
+            tc = timeit(lambda: dst.copy_(st), reps=50, warm=3)
+            print(f"noise AR update B={B:2d} C={C} {nlat}x{nlat} ({nbytes / 2e9:.2f} GB state) round {rnd}: kernel {tk:7.3f} ms "
+                  f"{nbytes / tk / 1e9:6.2f} TB/s = {tc / tk * 100:5.1f} % of the copy rate | copy {tc:7.3f} ms {nbytes / tc / 1e9:6.2f} TB/s | "
+                  f"torch formulation {tt:7.3f} ms = {tt / tk:5.1f} x the kernel", flush=True)
+        with torch.no_grad():
+            tf = timeit(lambda: m(), reps=5, warm=2)
+            tr = timeit(lambda: m.update(replace_state=True), reps=20, warm=2)
+        print(f"noise B={B:2d}: replace {tr:7.3f} ms | forward (inverse SHT of {B * T * C} planes) {tf:7.3f} ms = "
+              f"{tf / (tk + tf) * 100:5.1f} % of update + forward", flush=True)
+        del m, st, twin, dst
 
 
 if __name__ == "__main__":
