@@ -424,6 +424,32 @@ int mk_escore_finish(const float* sums, const float* scale, int nscale, float* l
 int mk_escore_grad(const void* f, int kind, const void* obs, const float* q, const float* w, const float* table, const float* gout,
                    void* gf, int B, int E, int C, int Cout, long long N, int S, int nanmode, float p, void* stream);
 
+/* Stage 2 of the Gaussian maximum mean discrepancy (GaussianMMDLoss, makani/utils/losses/mmd_loss.py:30-219) between
+ * mk_escore_sums (S = 1, p = beta, nanmode 1) and mk_escore_grad: sums (B, C, 1, K) -> k = exp(-s^2 / 2 sigma) of the (optionally
+ * channel-summed) sums, loss (B, Cout) = sum_e k_e / E - (E - 1 + alpha) / (E^2 (E - 1)) sum_{i<j} k_ij (0 spread for E = 1) and
+ * table (B, Cout, 1, K) = d loss / d sums. */
+int mk_mmd_finish(const float* sums, float* loss, float* table, int B, int E, int C, int reduce, float sigma, float alpha, void* stream);
+
+/* ---- adjusted mean squared error in spectral space (SpectralAMSELoss, makani/utils/losses/amse_loss.py:29-114) --------
+ * X, Y: (R, L, M) complex64 coefficient planes (re, im interleaved); wgt: optional (R, L, M) f32.  c_m = 1 for the global order
+ * m + m_off = 0, else 2; orders m > l + tri_off are structurally zero (tri_off = l_off - m_off of a shard).
+ * mk_amse_sums: sums (R, L, 3) = sum_m c_m wgt / 4 pi of |x|^2, |y|^2, Re(x conj y).
+ * mk_amse_grad: t (R, L, 3) = d loss / d sums -> dX = c_m wgt / 4 pi (2 t0 x + t2 y), dY (optional) = c_m wgt / 4 pi (2 t1 y + t2 x),
+ * complex64 in torch's complex-gradient convention, zeros at the structurally zero orders. */
+int mk_amse_sums(const float* X, const float* Y, const float* wgt, float* sums, long long R, int L, int M, int tri_off, int m_off,
+                 void* stream);
+int mk_amse_grad(const float* X, const float* Y, const float* wgt, const float* t, float* dX, float* dY, long long R, int L, int M,
+                 int tri_off, int m_off, void* stream);
+
+/* ---- Gaussian negative log likelihood of an ensemble (EnsembleNLLLoss, makani/utils/losses/likelihood_loss.py:30-134) ----
+ * f: (B, E, C, hw) members f32 | bf16, obs: (B, C, hw) f32, q: (hw), w: optional (B, C, hw) f32.
+ * nll = 0.5 (log s2 + (obs - mu)^2 / s2), mu the ensemble mean, s2 = max(centred variance (correction 0), eps^2).
+ * grad == 0: partial[(B * C) * mk_ens_nll_chunks(hw)] chunk sums of q * w * nll (the caller adds the chunks of a plane);
+ * grad == 1: gf (shape / dtype of f) = gout[b * C + c] * q * w * d nll / d f_e (no gradient through an active clamp).  1 <= E <= 32. */
+int mk_ens_nll_chunks(long long hw);
+int mk_ens_nll(const void* f, int f_dtype, const float* obs, const float* q, const float* w, const float* gout, float* partial, void* gf,
+               int B, int E, int C, long long hw, float eps, int grad, void* stream);
+
 /* ---- spectral noise processes on the sphere (makani/models/noise.py: BaseNoiseS2 / DiffusionNoiseS2 / DummyNoiseS2 update) ----
  * state: (B, T, C, L, M, 2) f32, updated in place in one pass (makani_amd/csrc/noise.hip).  s = reflect ? -1 : 1.
  *   MK_NOISE_WHITE:   state[:, t] = s xi[t]                                                     (T levels drawn)

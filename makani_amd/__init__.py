@@ -7,6 +7,7 @@ from .layers import MLP, EncoderDecoder, InstanceNorm2d, PointwiseConv, Geometri
 from .sfno import SphericalFourierNeuralOperatorNet, NeuralOperatorBlock, SpectralFilterLayer
 from .losses import CRPSLoss, GradientCRPSLoss, VortDivCRPSLoss, GeometricLpLoss, GridQuadrature, SpectralCRPSLoss, SpectralLpLoss, SpectralH1Loss
 from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss, SpectralL2EnergyScoreLoss
+from .losses import SpectralAMSELoss, EnsembleNLLLoss, GaussianMMDLoss
 from .stepper import MultiStepWrapper, SingleStepWrapper
 from .disco import DiscreteContinuousConvS2, ResampleS2
 from .fcn3 import AtmoSphericNeuralOperatorNet
@@ -17,5 +18,6 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "GridQuadrature", "SpectralLpLoss", "SpectralH1Loss", "CRPSLoss", "SpectralCRPSLoss", "GeometricInstanceNormS2", "MultiStepWrapper", "SingleStepWrapper",
            "DiscreteContinuousConvS2", "ResampleS2", "AtmoSphericNeuralOperatorNet",
            "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
+           "SpectralAMSELoss", "EnsembleNLLLoss", "GaussianMMDLoss",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
            "noise_seed_reflect"]

@@ -111,6 +111,11 @@ _SIGS = {
     "mk_escore_sums": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_int, c_f, c_vp], c_int),
     "mk_escore_finish": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_vp], c_int),
     "mk_escore_grad": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_ll, c_int, c_int, c_f, c_vp], c_int),
+    "mk_mmd_finish": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_f, c_vp], c_int),
+    "mk_amse_sums": ([c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "mk_amse_grad": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp], c_int),
+    "mk_ens_nll_chunks": ([c_ll], c_int),
+    "mk_ens_nll": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_f, c_int, c_vp], c_int),
     "mk_noise_update": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
     "mk_noise_advance": ([c_vp, c_ll, c_vp], c_int),
     "mk_disco_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),

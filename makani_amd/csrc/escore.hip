@@ -297,6 +297,40 @@ __global__ __launch_bounds__(ENT) void escore_finish_kernel(const float* __restr
     if (threadIdx.x == 0) loss[blockIdx.x] = red[0];
 }
 
+// Stage 2 of the Gaussian maximum mean discrepancy (GaussianMMDLoss, makani/utils/losses/mmd_loss.py:190-219) on the sums of
+// stage 1 (S = 1, p = beta): channel sum in channel order, k = exp(-s^2 / 2 sigma), the skill mean sum_e k_e / E and the spread
+// sum_{i != j} k_ij (E - 1 + alpha) / (E^2 (E - 1)) (every unordered pair twice; exactly 0 for E = 1), loss = skill - spread / 2.
+// grid: B * Cout blocks.  sums (B, C, 1, K) -> loss (B, Cout), table (B, Cout, 1, K) = d loss / d sums for mk_escore_grad
+__global__ __launch_bounds__(ENT) void mmd_finish_kernel(const float* __restrict__ sums, float* __restrict__ loss, float* __restrict__ table,
+                                                         int C, int Cout, int E, float sigma, float alpha) {
+    __shared__ float red[ENT];
+    const int b = blockIdx.x / Cout, co = blockIdx.x % Cout;
+    const int K = E + E * (E - 1) / 2;
+    const float fskill = 1.f / (float)E;
+    const float fpair = (E > 1) ? -((float)E - 1.f + alpha) / ((float)E * (float)E * (float)(E - 1)) : 0.f;
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < K; i += ENT) {
+        float v;
+        if (Cout == 1 && C > 1) {
+            v = 0.f;
+            for (int c = 0; c < C; ++c) v += sums[((long long)b * C + c) * K + i];
+        } else {
+            v = sums[((long long)b * C + co) * K + i];
+        }
+        const float k = expf(-0.5f * v * v / sigma);
+        const float fac = (i < E) ? fskill : fpair;
+        acc += fac * k;
+        table[((long long)b * Cout + co) * K + i] = -fac * k * v / sigma;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = ENT / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss[blockIdx.x] = red[0];
+}
+
 // ---- stage 3 -------------------------------------------------------------------------------------------------------------
 // grid: (chunks, S, planes * ntile).  A block owns the members [a0, a0 + EM) of its points and walks every tile for the partners.
 template <typename T, int PM, int EM>
@@ -474,6 +508,16 @@ extern "C" int mk_escore_finish(const float* sums, const float* scale, int nscal
     hipLaunchKernelGGL(escore_finish_kernel, dim3((unsigned)(B * Cout)), dim3(ENT), 0, (hipStream_t)stream, sums, scale, nscale, loss, table, C,
                        Cout, S, E, p, beta, alpha, eps);
     return mk_check_launch("mk_escore_finish");
+}
+
+extern "C" int mk_mmd_finish(const float* sums, float* loss, float* table, int B, int E, int C, int reduce, float sigma, float alpha,
+                             void* stream) {
+    MK_REQUIRE(sums && loss && table && B > 0 && E >= 1 && E <= EMAX && C > 0 && sigma > 0.f,
+               "mmd_finish: bad arguments (1 <= E <= 32, sigma > 0)");
+    const int Cout = reduce ? 1 : C;
+    hipLaunchKernelGGL(mmd_finish_kernel, dim3((unsigned)(B * Cout)), dim3(ENT), 0, (hipStream_t)stream, sums, loss, table, C, Cout, E, sigma,
+                       alpha);
+    return mk_check_launch("mk_mmd_finish");
 }
 
 extern "C" int mk_escore_grad(const void* f, int kind, const void* obs, const float* q, const float* w, const float* table, const float* gout,

@@ -1118,3 +1118,283 @@ class SpectralL2EnergyScoreLoss(_SpectralEnergyScore):
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
                 **kwargs) -> torch.Tensor:
         return self._score(forecasts, observations, per_degree=True)
+
+
+# --------------------------------------------------------------------------- #
+# adjusted MSE, ensemble likelihood, Gaussian MMD (makani/utils/losses/amse_loss.py, likelihood_loss.py, mmd_loss.py)
+# --------------------------------------------------------------------------- #
+class AmseSumsFn(torch.autograd.Function):
+    """``csrc/amse.hip``: X, Y (B, C, L, M) complex64 and an optional weight (B, C, L, M) -> sums (B, C, L, 3): the Parseval
+    sums over the orders of |x|^2, |y|^2 and Re(x conj y), with the 1 / 4 pi.  The backward reads X and Y once and writes both
+    gradients (the target's only when it is asked for)."""
+
+    @staticmethod
+    def forward(ctx, X, Y, wgt, tri_off, m_off):
+        B, Cc, L, M = X.shape
+        x = torch.view_as_real(X.to(torch.complex64).contiguous())
+        y = torch.view_as_real(Y.to(torch.complex64).contiguous())
+        w = wgt.float().contiguous() if wgt is not None else None
+        sums = torch.empty((B, Cc, L, 3), dtype=torch.float32, device=x.device)
+        check(lib().mk_amse_sums(ptr(x), ptr(y), ptr(w), ptr(sums), B * Cc, L, M, tri_off, m_off, stream()), "mk_amse_sums")
+        ctx.save_for_backward(x, y, w if w is not None else torch.empty(0, device=x.device))
+        ctx.meta = (w is not None, tri_off, m_off)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, w = ctx.saved_tensors
+        has_w, tri_off, m_off = ctx.meta
+        B, Cc, L, M = x.shape[:4]
+        t = g.float().contiguous()
+        dx = torch.empty_like(x)
+        dy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        check(lib().mk_amse_grad(ptr(x), ptr(y), ptr(w) if has_w else None, ptr(t), ptr(dx), ptr(dy), B * Cc, L, M, tri_off, m_off,
+                                 stream()), "mk_amse_grad")
+        return torch.view_as_complex(dx), (torch.view_as_complex(dy) if dy is not None else None), None, None, None
+
+
+class SpectralAMSELoss(SpectralLpLoss):
+    """``SpectralAMSELoss`` of ``makani/utils/losses/amse_loss.py:29-114`` ("amse", arXiv:2501.19374): per degree l the power of
+    prediction and target and their coherence, ``(|x| - |y|)^2 + 2 max(|x|^2, |y|^2) (1 - coh)``, summed over l.
+    ``forward(prd (B, C, H, W), tar (B, C, H, W), wgt=None) -> (B, C)``.  HIP SHT (fp32, autocast off), then ONE kernel for the
+    three Parseval sums of a degree (``csrc/amse.hip``) and one for both gradients; the finish of :100-110 works on the
+    (B, C, L, 3) sums in torch.  ``spatial_distributed``: the sums are added over the "w" group before the finish, the loss
+    over the "h" group after it.  The sums are kept in fp32 whatever the input dtype; the result is cast to it."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, spatial_distributed: Optional[bool] = False,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed=spatial_distributed, eps=eps)
+
+    @property
+    def type(self):
+        return "deterministic"                                                  # LossType.Deterministic
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, prd: torch.Tensor, tar: torch.Tensor, wgt: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        if prd.dim() != 4:
+            raise ValueError(f"expected (B, C, H, W), got {tuple(prd.shape)}")
+        if not prd.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        from . import comm as _comm
+        ptype = prd.dtype
+        with torch.autocast(device_type=prd.device.type, enabled=False):
+            x = self.sht(prd.float())
+            y = self.sht(tar.float())
+        B, Cc, L, M = x.shape
+        w = wgt.to(x.device).expand(B, Cc, L, M) if wgt is not None else None
+        sums = AmseSumsFn.apply(x, y, w, self._l_off - self._m_off, self._m_off)
+        if self.spatial_distributed and _comm.get_size("w") > 1:
+            sums = _ReduceFromGroupFn.apply(sums, _comm.get_group("w"))
+        xnorm2, ynorm2, xycoh_sum = sums.unbind(-1)
+        xnorm, ynorm = torch.sqrt(xnorm2), torch.sqrt(ynorm2)
+        xycoh = xycoh_sum / torch.sqrt(xnorm2 * ynorm2 + self.eps)             # eps inside the root (:104)
+        loss = torch.square(xnorm - ynorm) + 2 * torch.maximum(xnorm2, ynorm2) * (1 - xycoh)
+        loss = torch.sum(loss, dim=-1)
+        if self.spatial_distributed and _comm.get_size("h") > 1:
+            loss = _ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+        return loss.to(ptype)
+
+
+class EnsNllFn(torch.autograd.Function):
+    """out[b, c] = sum_p q[p] * w[b, c, p] * nll(obs[b, c, p], forecasts[b, :, c, p]) (``csrc/ensnll.hip``); gradient with
+    respect to the forecasts.  forecasts (B, E, C, N) f32 | bf16 read in place, obs (B, C, N)."""
+
+    @staticmethod
+    def forward(ctx, forecasts, obs, q, wgt, eps):
+        B, E, Cc, N = forecasts.shape
+        f = _prep(forecasts)
+        o = obs.float().contiguous()
+        q = q.float().contiguous()
+        w = wgt.float().contiguous() if wgt is not None else None
+        ch = lib().mk_ens_nll_chunks(N)
+        partial = torch.empty((B * Cc, ch), dtype=torch.float32, device=f.device)
+        check(lib().mk_ens_nll(ptr(f), dtype_code(f), ptr(o), ptr(q), ptr(w), None, ptr(partial), None, B, E, Cc, N, float(eps), 0,
+                               stream()), "mk_ens_nll")
+        ctx.save_for_backward(f, o, q, w if w is not None else torch.empty(0, device=f.device))
+        ctx.meta = (float(eps), w is not None, forecasts.dtype)
+        return partial.sum(dim=1).reshape(B, Cc)
+
+    @staticmethod
+    def backward(ctx, g):
+        f, o, q, w = ctx.saved_tensors
+        eps, has_w, dt = ctx.meta
+        B, E, Cc, N = f.shape
+        gf = torch.empty_like(f)
+        go = g.float().contiguous()
+        check(lib().mk_ens_nll(ptr(f), dtype_code(f), ptr(o), ptr(q), ptr(w) if has_w else None, ptr(go), None, ptr(gf), B, E, Cc, N,
+                               eps, 1, stream()), "mk_ens_nll")
+        return gf.to(dt), None, None, None, None
+
+
+def _ensemble_size_check(E, what):
+    if E > MAX_ENSEMBLE:
+        raise NotImplementedError(f"ensemble size {E}: the HIP {what} kernels are built for 1 <= E <= {MAX_ENSEMBLE}")
+
+
+class EnsembleNLLLoss(nn.Module):
+    """``EnsembleNLLLoss`` of ``makani/utils/losses/likelihood_loss.py:30-134`` ("ensemble_nll"): the negative log likelihood of
+    the observation under a Gaussian with the ensemble's mean and (``correction=0``) variance, the variance clamped at
+    ``eps^2``, under the quadrature.  ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W), spatial_weights=None)
+    -> (B, C)``.  Score and quadrature are one HIP kernel (``csrc/ensnll.hip``), the gradient with respect to the forecasts
+    one more; 1 <= E <= 32 (more: NotImplementedError).  ``ensemble_distributed`` / ``spatial_distributed`` as ``CRPSLoss``."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__()
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
+        self.spatial_distributed = self.quadrature.distributed
+        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.eps = eps
+        # (the whole plane's weights: the ensemble-parallel path takes this rank's share of the points in forward, as CRPSLoss does)
+        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
+    @property
+    def n_channels(self):
+        return len(self.channel_names)
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        B, E, Cc, H, W = forecasts.shape               # (a forecast without an ensemble axis fails here, as in the reference)
+        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
+            raise ValueError("the weights have to have the same number of dimensions as observations")
+        if not self.ensemble_distributed:
+            _ensemble_size_check(E, "likelihood")
+        if not forecasts.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        f = forecasts.reshape(B, E, Cc, H * W)
+        o = observations.reshape(B, Cc, H * W)
+        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
+        q = self.quad_weight_split.reshape(-1)
+        if self.ensemble_distributed:               # members <-> a share of the points (:108-118), the shares summed (:127-128)
+            f, o, q, w, group = _ensemble_split(f, o, q, w)
+            _ensemble_size_check(f.shape[1], "likelihood")
+            return self.quadrature._reduce(_ReduceFromGroupFn.apply(EnsNllFn.apply(f, o, q, w, self.eps), group))
+        return self.quadrature._reduce(EnsNllFn.apply(f, o, q, w, self.eps))
+
+
+class MmdFn(EnergyScoreFn):
+    """``GaussianMMDLoss`` on the energy-score pipeline: stage 1 (``mk_escore_sums``, p = beta, one segment, a NaN observation
+    or member masks the point), the sums added over ``sum_groups``, ``mk_mmd_finish`` -> loss (B, C_out) and the table
+    d loss / d sums; the backward is stage 3 (``mk_escore_grad``) as inherited."""
+
+    @staticmethod
+    def forward(ctx, forecasts, obs, q, wgt, reduce, beta, sigma, alpha, sum_groups):
+        B, E, Cc, N = forecasts.shape
+        f = _prep(forecasts)
+        kind = dtype_code(f)
+        o = obs.float().contiguous()
+        q = q.float().contiguous()
+        w = wgt.float().contiguous() if wgt is not None else None
+        K = E + E * (E - 1) // 2
+        sums = torch.empty((B, Cc, 1, K), dtype=torch.float32, device=f.device)
+        nws = lib().mk_escore_sums_workspace(B, E, Cc, N, 1, 1)
+        ws = torch.empty((nws,), dtype=torch.float32, device=f.device) if nws else None
+        check(lib().mk_escore_sums(ptr(f), kind, ptr(o), ptr(q), ptr(w), ptr(sums), ptr(ws), B, E, Cc, N, 1, 1, float(beta), stream()),
+              "mk_escore_sums")
+        from . import ops
+        for group in sum_groups:
+            ops._all_reduce_sum(sums, group)
+        Cout = 1 if reduce else Cc
+        loss = torch.empty((B, Cout), dtype=torch.float32, device=f.device)
+        table = torch.empty((B, Cout, 1, K), dtype=torch.float32, device=f.device)
+        check(lib().mk_mmd_finish(ptr(sums), ptr(loss), ptr(table), B, E, Cc, int(reduce), float(sigma), float(alpha), stream()),
+              "mk_mmd_finish")
+        ctx.save_for_backward(f, o, q, w if w is not None else torch.empty(0, device=f.device), table)
+        ctx.meta = (kind, w is not None, 1, 1, float(beta), forecasts.dtype)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        return EnergyScoreFn.backward(ctx, g)[:1] + (None,) * 8
+
+
+class GaussianMMDLoss(nn.Module):
+    """``GaussianMMDLoss`` of ``makani/utils/losses/mmd_loss.py:30-219`` ("gaussian_mmd", arXiv:1505.03906): with the distances
+    s(a, b) = sum_n q w |a_n - b_n|^beta (per channel, or summed over the channels with ``channel_reduction``) and the kernel
+    k = exp(-s^2 / 2 sigma):  mean_e k(o, f_e) - (E - 1 + alpha) / (2 E^2 (E - 1)) sum_{i != j} k(f_i, f_j).
+    ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W), spatial_weights=None) -> (B, C) | (B, 1)``.  A point where
+    the observation or any member is NaN is dropped.  Stages 1 and 3 of ``csrc/escore.hip`` with ``mk_mmd_finish`` between
+    them: the members are read in place and no pair tensor exists.  1 <= E <= 32 (more: NotImplementedError).
+
+    Deviations, stated: ``beta < 1`` raises NotImplementedError, as ``LpEnergyScoreLoss`` does for ``p < 1``.
+    ``channel_reduction=True`` sums the distances over the CHANNELS and returns (B, 1), as the reference's comment, its
+    ``n_channels`` and the energy scores say; the reference's ``sum(dim=-2)`` (:192-194) falls on the batch axis of its
+    (E, B, C) distances and returns (1, C)."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
+                 sigma: Optional[float] = 1.0, alpha: Optional[float] = 1.0, beta: Optional[float] = 2.0,
+                 channel_reduction: Optional[bool] = False, **kwargs):
+        super().__init__()
+        if float(beta) < 1.0:
+            raise NotImplementedError(f"beta = {beta}: the Gaussian MMD is built for beta >= 1 (the gradient of |d|^beta is unbounded "
+                                      "at coincident members for beta < 1)")
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
+        self.spatial_distributed = self.quadrature.distributed
+        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.alpha, self.beta, self.channel_reduction, self.sigma = alpha, beta, channel_reduction, sigma
+        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
+        self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
+    @property
+    def n_channels(self):
+        return 1 if self.channel_reduction else len(self.channel_names)
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: str = None) -> torch.Tensor:
+        return torch.ones(1)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        if forecasts.dim() != 5:
+            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
+        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
+            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
+                             f"observations (found {observations.dim()}).")
+        if self.ensemble_weights is not None:
+            raise NotImplementedError("currently only constant ensemble weights are supported")
+        B, E, Cc, H, W = forecasts.shape
+        if not self.ensemble_distributed:
+            _ensemble_size_check(E, "MMD")
+        if not forecasts.is_cuda:
+            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        f = forecasts.reshape(B, E, Cc, H * W)
+        o = observations.reshape(B, Cc, H * W)
+        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
+        q = self.quad_weight_split.reshape(-1)
+        groups = []
+        if self.ensemble_distributed:               # members <-> a share of the points (:131-145), the sums added over the group (:180-182)
+            f, o, q, w, group = _ensemble_split(f, o, q, w)
+            groups.append(group)
+            _ensemble_size_check(f.shape[1], "MMD")
+        if self.spatial_distributed:
+            from . import distributed as thd
+            groups.append(thd.spatial_group())
+        return MmdFn.apply(f, o, q, w, self.channel_reduction, self.beta, self.sigma, self.alpha, groups)

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [losses]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -335,6 +335,95 @@ def escore():
                 line += f" | torch formula fwd {timeit(torch_ref, reps=5, warm=1):7.3f} ms"
             print(line, flush=True)
             del f, o, gf
+
+
+def losses():
+    """SpectralAMSELoss, EnsembleNLLLoss and GaussianMMDLoss, forward + backward, at 721 x 1440, C = 73, B = 1, E = 2 and 16,
+    beside the reference formula in plain torch on the same GPU, in the same process, the two timed in turn over three rounds.
+    Achieved bytes/s over the ALGORITHMIC traffic as a fraction of the HBM roof: NLL reads the members once (plus observation
+    and quadrature weights) and writes their gradient once; AMSE (kernels alone, on coefficient planes) reads two planes and
+    writes two.  MMD's torch formula is timed at E = 2 only (its pair tensor grows with E^2)."""
+    PEAK = 8.0e12
+    H, W, C, B = 721, 1440, 73, 1
+    N = H * W
+    kw = dict(img_shape=(H, W), crop_shape=(H, W), crop_offset=(0, 0), channel_names=[str(c) for c in range(C)], grid_type="equiangular")
+    pct = lambda nbytes, ms: nbytes / (ms * 1e-3) / PEAK * 100
+
+    def fb(fn, *xs):
+        def run():
+            for x in xs:
+                x.grad = None
+            fn().sum().backward()
+        return run
+
+    # ---- AMSE: the two kernels on coefficient planes, and the module with its transforms
+    amse = ma.SpectralAMSELoss(**kw).to(dev)
+    L, M = amse.sht.lmax, amse.sht.mmax
+    X = torch.randn(B, C, L, M, dtype=torch.complex64, device=dev).requires_grad_(True)
+    Y = torch.randn(B, C, L, M, dtype=torch.complex64, device=dev).requires_grad_(True)
+    from makani_amd.losses import AmseSumsFn
+
+    def finish(sums):
+        a, b, c = sums.unbind(-1)
+        coh = c / torch.sqrt(a * b + 1e-6)
+        return (torch.square(torch.sqrt(a) - torch.sqrt(b)) + 2 * torch.maximum(a, b) * (1 - coh)).sum(-1)
+
+    def amse_torch():
+        inv = 1.0 / (4.0 * math.pi)
+        xx, yy, xy = torch.square(torch.abs(X)), torch.square(torch.abs(Y)), torch.real(X * Y.conj())
+        return finish(torch.stack([inv * (v[..., 0] + 2 * torch.sum(v[..., 1:], dim=-1)) for v in (xx, yy, xy)], dim=-1))
+
+    k_amse = fb(lambda: finish(AmseSumsFn.apply(X, Y, None, 0, 0)), X, Y)
+    t_amse = fb(amse_torch, X, Y)
+    nbytes = 4 * B * C * L * M * 8 + 2 * B * C * L * M * 8         # backward: two planes read, two written; forward: two read
+    for rnd in range(3):
+        tk, tt = timeit(k_amse, reps=30, warm=3), timeit(t_amse, reps=10, warm=2)
+        print(f"losses AMSE kernels on ({B * C}, {L}, {M}) planes round {rnd}: fwd + bwd {tk:7.3f} ms {pct(nbytes, tk):5.1f} % of the HBM roof "
+              f"({nbytes / 1e9:.2f} GB) | torch formula {tt:7.3f} ms = {tt / tk:5.1f} x", flush=True)
+    prd = torch.randn(B, C, H, W, device=dev).requires_grad_(True)
+    tar = torch.randn(B, C, H, W, device=dev)
+    tm = timeit(fb(lambda: amse(prd, tar), prd), reps=10, warm=2)
+    print(f"losses AMSE module (two analyses, kernels, one adjoint analysis) fwd + bwd {tm:7.3f} ms", flush=True)
+    del X, Y, prd, tar
+
+    q = (torch.rand(N, device=dev) / N).view(1, 1, N)
+    for E in (2, 16):
+        f = torch.randn(B, E, C, H, W, device=dev).requires_grad_(True)
+        o = torch.randn(B, C, H, W, device=dev)
+        # ---- NLL
+        nll = ma.EnsembleNLLLoss(**kw).to(dev)
+
+        def nll_torch():
+            s2, mu = torch.var_mean(f.reshape(B, E, C, N), dim=1, correction=0)
+            s2 = torch.clamp(s2, min=1e-12)
+            return torch.sum(0.5 * (torch.log(s2) + torch.square(o.reshape(B, C, N) - mu) / s2) * q, dim=-1)
+
+        nbytes = C * N * 4 * (2 * (E + 1) + E) + 2 * N * 4          # forward and backward read members + observation, backward writes E
+        k, t = fb(lambda: nll(f, o), f), fb(nll_torch, f)
+        for rnd in range(3):
+            tk, tt = timeit(k, reps=20, warm=3), timeit(t, reps=5, warm=2)
+            print(f"losses NLL E={E:2d} round {rnd}: fwd + bwd {tk:7.3f} ms {pct(nbytes, tk):5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | "
+                  f"torch formula {tt:7.3f} ms = {tt / tk:5.1f} x", flush=True)
+        # ---- MMD
+        mmd = ma.GaussianMMDLoss(sigma=4.0, **kw).to(dev)
+
+        def mmd_torch():
+            fe = torch.moveaxis(f, 1, 0).reshape(E, B, C, N)
+            sp = torch.sum((fe.unsqueeze(1) - fe.unsqueeze(0)).abs().pow(2.0) * q, dim=-1)
+            sk = torch.sum((o.reshape(1, B, C, N) - fe).abs().pow(2.0) * q, dim=-1)
+            sp, sk = torch.exp(-0.5 * torch.square(sp) / 4.0), torch.exp(-0.5 * torch.square(sk) / 4.0)
+            sp = torch.where(torch.eye(E, device=dev).bool().reshape(E, E, 1, 1), 0.0, sp)
+            return sk.sum(0) / E - 0.5 * sp.sum(dim=(0, 1)) * E / (E * E * (E - 1))
+
+        k = fb(lambda: mmd(f, o), f)
+        for rnd in range(3):
+            tk = timeit(k, reps=10, warm=2)
+            line = f"losses MMD E={E:2d} round {rnd}: fwd + bwd {tk:7.3f} ms {pct(nbytes, tk):5.1f} % of the HBM roof on single-pass traffic"
+            if E == 2:
+                tt = timeit(fb(mmd_torch, f), reps=5, warm=2)
+                line += f" | torch formula {tt:7.3f} ms = {tt / tk:5.1f} x"
+            print(line, flush=True)
+        del f, o
 
 
 def noise():
