@@ -450,6 +450,34 @@ int mk_ens_nll_chunks(long long hw);
 int mk_ens_nll(const void* f, int f_dtype, const float* obs, const float* q, const float* w, const float* gout, float* partial, void* gf,
                int B, int E, int C, long long hw, float eps, int grad, void* stream);
 
+/* ---- plane sums of the geometric validation metrics (makani/utils/metrics/functions.py:29-677) ----------------------------
+ * q: (N) quadrature weights, w: optional (B, C, N) f32 spatial weights, ws: workspace, out: fp32.  Every block writes the sums
+ * of its chunk of a plane to ws, a second launch adds the mk_metric_chunks(N) chunks of a plane in chunk order: repeats are
+ * bit-identical.  Entries of out not selected by `which` are not written.  16-byte accesses when N is a multiple of 4 and every
+ * pointer is 16-byte aligned, scalar ones otherwise.  B * C <= 65535.
+ * mk_metric_det_sums: x, y (B, C, N) f32 | bf16 each, bias optional (C, N) f32 (GeometricACC's climatology, :184-188).
+ *   out (B, C, 5) = sum_p q w {|x - y|, (x - y)^2, x'y', x'^2, y'^2}, x' = x - bias, y' = y - bias; which: bit k selects sum k
+ *   (MK_METRIC_L1 GeometricL1 :53-71, MK_METRIC_L2 GeometricRMSE :110-132, MK_METRIC_XY | XX | YY GeometricACC :184-218);
+ *   ws: B * C * mk_metric_chunks(N) * 5 floats.
+ * mk_metric_ens_sums: f (B, E, C, N) members f32 | bf16 read in place, obs (B, C, N) f32, 1 <= E <= 32.
+ *   out (B, C, E + 3): [0] skill = sum_p q w (mu - obs)^2, [1] spread = sum_p q w sum_e (mu - f_e)^2 (GeometricSSR :394-414,
+ *   GeometricSpread :287-299; mean first, then centred squares), [2 + k] = sum_p q w [r = k] for r = #{e : f_e <= obs}, the
+ *   insertion index of sort + searchsorted(side="right") + one_hot (GeometricRankHistogram :639-656) for finite inputs;
+ *   which: MK_METRIC_SKILL | MK_METRIC_SPREAD | MK_METRIC_HIST; ws: B * C * mk_metric_chunks(N) * (E + 3) floats. */
+#define MK_METRIC_L1 1
+#define MK_METRIC_L2 2
+#define MK_METRIC_XY 4
+#define MK_METRIC_XX 8
+#define MK_METRIC_YY 16
+#define MK_METRIC_SKILL 1
+#define MK_METRIC_SPREAD 2
+#define MK_METRIC_HIST 4
+int mk_metric_chunks(long long N);
+int mk_metric_det_sums(const void* x, int x_dtype, const void* y, int y_dtype, const float* bias, const float* w, const float* q,
+                       float* out, float* ws, int B, int C, long long N, int which, void* stream);
+int mk_metric_ens_sums(const void* f, int f_dtype, const float* obs, const float* w, const float* q, float* out, float* ws, int B,
+                       int E, int C, long long N, int which, void* stream);
+
 /* ---- spectral noise processes on the sphere (makani/models/noise.py: BaseNoiseS2 / DiffusionNoiseS2 / DummyNoiseS2 update) ----
  * state: (B, T, C, L, M, 2) f32, updated in place in one pass (makani_amd/csrc/noise.hip).  s = reflect ? -1 : 1.
  *   MK_NOISE_WHITE:   state[:, t] = s xi[t]                                                     (T levels drawn)

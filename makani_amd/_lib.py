@@ -116,6 +116,9 @@ _SIGS = {
     "mk_amse_grad": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp], c_int),
     "mk_ens_nll_chunks": ([c_ll], c_int),
     "mk_ens_nll": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_f, c_int, c_vp], c_int),
+    "mk_metric_chunks": ([c_ll], c_int),
+    "mk_metric_det_sums": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_int, c_vp], c_int),
+    "mk_metric_ens_sums": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_vp], c_int),
     "mk_noise_update": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
     "mk_noise_advance": ([c_vp, c_ll, c_vp], c_int),
     "mk_disco_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),

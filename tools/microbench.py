@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [losses]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [losses] [metrics]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -424,6 +424,66 @@ def losses():
                 line += f" | torch formula {tt:7.3f} ms = {tt / tk:5.1f} x"
             print(line, flush=True)
         del f, o
+
+
+def metrics():
+    """The plane sums of the validation metrics (csrc/metrics.hip), forward only, at 721 x 1440, C = 73, B = 1, E = 2 and 16, beside
+    the reference formulation in plain torch on the same GPU, in the same process, the two timed in turn over three rounds.
+    Achieved bytes/s over the ALGORITHMIC traffic: x + y (+ bias, weight) once for the deterministic sums, E + 1 planes once for
+    the ensemble sums (plus the quadrature weights)."""
+    from makani_amd import metrics as mm
+    PEAK = 8.0e12
+    H, W, C, B = 721, 1440, 73, 1
+    N = H * W
+    quad = ma.GridQuadrature("naive", (H, W)).to(dev)
+    q = quad.quad_weight
+    rate = lambda nbytes, ms: f"{nbytes / (ms * 1e-3) / 1e12:5.2f} TB/s = {nbytes / (ms * 1e-3) / PEAK * 100:5.1f} % of the HBM roof"
+    with torch.no_grad():
+        x, y = torch.randn(B, C, H, W, device=dev), torch.randn(B, C, H, W, device=dev)
+        bias, w = torch.randn(C, H, W, device=dev), torch.rand(B, C, H, W, device=dev) + 0.5
+
+        def rmse_torch():
+            return torch.sum(torch.square(x - y) * q, dim=(-2, -1))
+
+        def acc_torch():
+            xb, yb = x - bias, y - bias
+            return (torch.sum(xb * yb * q, dim=(-2, -1)), torch.sum(torch.square(xb) * q, dim=(-2, -1)), torch.sum(torch.square(yb) * q, dim=(-2, -1)))
+
+        forms = [("RMSE sum", lambda: ma.deterministic_sums(x, y, quad, which=mm.SUM_L2), rmse_torch, (2 * B * C + 1) * N * 4),
+                 ("ACC sums, bias", lambda: ma.deterministic_sums(x, y, quad, bias=bias, which=mm.SUM_ACC), acc_torch, (2 * B * C + C + 1) * N * 4),
+                 ("all five, bias, weight", lambda: ma.deterministic_sums(x, y, quad, bias=bias, weight=w),
+                  lambda: (rmse_torch(), acc_torch(), torch.sum(torch.abs(x - y) * q, dim=(-2, -1))), (3 * B * C + C + 1) * N * 4)]
+        for name, k, t, nbytes in forms:
+            for rnd in range(3):
+                tk, tt = timeit(k, reps=30, warm=3), timeit(t, reps=10, warm=2)
+                print(f"metrics {name} round {rnd}: {tk:7.3f} ms {rate(nbytes, tk)} ({nbytes / 1e9:.2f} GB) | torch formulation"
+                      f"{' (RMSE + ACC + L1, no weight)' if name.startswith('all') else ''} {tt:7.3f} ms = {tt / tk:5.1f} x", flush=True)
+        del x, y, bias, w
+        for E in (2, 16):
+            f, o = torch.randn(B, E, C, H, W, device=dev), torch.randn(B, C, H, W, device=dev)
+            f4, o3, qn = f.reshape(B, E, C, N), o.reshape(B, C, N), q.reshape(-1)
+            nbytes = ((E + 1) * B * C + 1) * N * 4
+
+            def ssr_torch():
+                mean = torch.sum(f, dim=1) / float(E)
+                skill = torch.square(mean - o)
+                spread = torch.sum(torch.square(mean.unsqueeze(1) - f), dim=1) / float(E - 1)
+                return torch.sum(skill * q, dim=(-2, -1)), torch.sum(spread * q, dim=(-2, -1))
+
+            def hist_torch():
+                fs, _ = torch.sort(torch.moveaxis(f4, 1, -1), dim=-1, descending=False, stable=True)
+                ins = torch.searchsorted(fs.contiguous(), o3.unsqueeze(-1).contiguous(), side="right").squeeze(-1)
+                return torch.sum(torch.nn.functional.one_hot(ins, num_classes=E + 1).to(torch.float32) * qn.reshape(1, 1, -1, 1), dim=2)
+
+            forms = [("skill + spread", lambda: mm._ens_launch(f4, o3, qn, None, 3), ssr_torch),
+                     ("rank histogram", lambda: mm._ens_launch(f4, o3, qn, None, 4), hist_torch),
+                     ("all three", lambda: mm._ens_launch(f4, o3, qn, None, 7), lambda: (ssr_torch(), hist_torch()))]
+            for name, k, t in forms:
+                for rnd in range(3):
+                    tk, tt = timeit(k, reps=20, warm=3), timeit(t, reps=3, warm=1)
+                    print(f"metrics E={E:2d} {name} round {rnd}: {tk:7.3f} ms {rate(nbytes, tk)} ({nbytes / 1e9:.2f} GB) | torch formulation "
+                          f"{tt:8.3f} ms = {tt / tk:6.1f} x", flush=True)
+            del f, o, f4, o3
 
 
 def noise():
