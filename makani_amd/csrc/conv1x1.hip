@@ -411,18 +411,36 @@ __global__ __launch_bounds__(NT, WGS) void conv_nn_kernel(const ConvNN p, int ti
 // 32 KB bf16 staging image in LDS with 8-byte stores; from there every thread handles whole 16-byte pixel vectors of
 // one channel row (epilogue math, coalesced 512-byte row segments to global memory).
 // The first two stages of the next tile are requested before the epilogue of the current one starts.
+//
+// TM = 6, the 384-row tile (plain and + bias only; conv_nn_ring_rows picks it for 384 <- 768): per 256 pixels one tile ingests
+// 384 x K weights + K x 256 activations where two 192-row tiles ingest the activations twice — 10 bytes per output element
+// instead of 14 — with the k-tiles, the k16-steps and hence the sum of every output element as in the 192-row tile.  What differs:
+//   registers   192 of the 256 per lane are accumulators.  The per-lane addresses of the DMA requests are recomputed inside every
+//               request from an opaque copy of the lane id, the fragment addresses of a k16-step are one XOR away from those of the
+//               first, and the bias is fetched between the k-loop and the epilogue (nothing is in flight there to stall on).
+//   LDS         two stages of 80 KB are all 160 KB: the staging image lies over the first 32 KB of stage 0 (weight rows 0 .. 255).
+//               Before the epilogue the next tile's stage 1 and what of its stage 0 the image does not cover are requested, the
+//               covered 32 KB after the epilogue's last barrier; the wait of the first k-tile is a full drain either way.
 template <int TM>                // TM = 32-row channel tiles per wave (BM = 2 * TM * 32)
 __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, int tilesM, long long tilesN, long long ntiles) {
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int TN = 2;                               // 8 waves = 2 (channels) x 4 (pixels); wave tile (TM*32) x 64
     constexpr int BM = 2 * TM * 32, BN = 256, BK = 64;
+    constexpr bool WIDE = TM == 6;                      // the 384-row tile
     constexpr int ASZ = BM * 128, XSZ = BK * BN * 2, STAGE = ASZ + XSZ;
     constexpr int NIA = BM / 64, NIX = 4, NI = NIA + NIX;     // LDS-DMA instructions per wave and stage
     constexpr int EROWS = 64;                           // staging image: 64 channel rows x 256 pixels bf16 = 32 KB
-    __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE + EROWS * 512];
-    unsigned char* const stg = smem + 2 * STAGE;
+    static_assert(!WIDE || EROWS * 512 == 4 * 8192, "the staging image covers the first four weight row groups of stage 0");
+    __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE + (WIDE ? 0 : EROWS * 512)];
+    unsigned char* const stg = WIDE ? smem : smem + 2 * STAGE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wv = WIDE ? __builtin_amdgcn_readfirstlane(wave) : wave;      // (384-row tile: the wave id as a scalar)
+    auto lane_here = [&]() __attribute__((always_inline)) {                 // see conv_nn_astat2_kernel
+        int l = lane;
+        asm volatile("" : "+v"(l));
+        return l;
+    };
     const int wm = wave >> 2, wn = wave & 3;
     const int l31 = lane & 31, lh = lane >> 5;
     const int nk = (p.K + BK - 1) / BK;                 // the last k-tile may be ragged: its missing activation rows read zeros
@@ -459,6 +477,7 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
     const u16* xb = p.X;                                // activations of the batch entry being multiplied
     int m0 = 0, bcur = -1;
     long long n0 = 0;
+    int cmax_t = 0;                                     // 384-row tile: last valid 16-byte chunk of the tile's activation rows
 
     auto setup_tile = [&](long long t) {                // per-tile DMA addresses (tiles of one pixel range are consecutive ids)
         const int tm = (int)(t % tilesM);
@@ -470,39 +489,64 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
             bcur = b;
             xb = p.X + (long long)b * p.K * p.N;
         }
+        if constexpr (WIDE) {                           // (scalars only: issue() works the per-lane offsets out)
+            cmax_t = (int)((min(p.N, n0 + BN) - n0) / 8) - 1;
+        } else {
 #pragma unroll
-        for (int i = 0; i < NIA; ++i) {
-            const int row = min(m0 + (wave + 8 * i) * 8 + (lane >> 3), p.M - 1);     // rows past M: any valid row (never stored)
-            voffa[i] = (unsigned)row * (unsigned)(p.lda * 2) + (unsigned)ca_log * 16u;
+            for (int i = 0; i < NIA; ++i) {
+                const int row = min(m0 + (wave + 8 * i) * 8 + (lane >> 3), p.M - 1);     // rows past M: any valid row (never stored)
+                voffa[i] = (unsigned)row * (unsigned)(p.lda * 2) + (unsigned)ca_log * 16u;
+            }
+            // pixels past N (last pixel tile): re-read the last valid chunk of the row (those columns are never stored)
+            const int cmax = (int)((min(p.N, n0 + BN) - n0) / 8) - 1;
+#pragma unroll
+            for (int j = 0; j < NIX; ++j) voffx_t[j] = voffx[j] - (unsigned)max(0, cx_log - cmax) * 16u;
         }
-        // pixels past N (last pixel tile): re-read the last valid chunk of the row (those columns are never stored)
-        const int cmax = (int)((min(p.N, n0 + BN) - n0) / 8) - 1;
-#pragma unroll
-        for (int j = 0; j < NIX; ++j) voffx_t[j] = voffx[j] - (unsigned)max(0, cx_log - cmax) * 16u;
     };
-    auto issue = [&](int kt, int stage) {
+    // part (384-row tile only): 0 = the whole stage, 1 = all of it but the weight row groups 0 .. 3 (the 32 KB the staging image
+    // lies over), 2 = those four
+    auto issue = [&](int kt, int stage, int part = 0) __attribute__((always_inline)) {
         const unsigned dst = lds_w + stage * STAGE;
         const unsigned soffa = (unsigned)(kt * BK * 2);
         // activations: a buffer per k-tile that ends with the tile's last existing input channel (rows k >= K read zeros);
         // offsets inside it stay below 64 rows (any K x N fits)
         const v4i_t rsX = make_rsrc_n(xb + (long long)kt * BK * p.N, (unsigned)min(BK, p.K - kt * BK) * rowbytes);
         const unsigned soffx = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(n0 * 2));
-        if constexpr (NIA == 4) dma4<8192>(dst, rsA, soffa, voffa[0], voffa[1], voffa[2], voffa[3]);
-        else dma3<8192>(dst, rsA, soffa, voffa[0], voffa[1], voffa[2]);
-        dma4<8192>(dst + ASZ, rsX, soffx, voffx_t[0], voffx_t[1], voffx_t[2], voffx_t[3]);
+        if constexpr (WIDE) {                           // the same offsets as voffa / voffx_t below, from the lane id
+            const int ln = lane_here();
+            const unsigned ca16 = (unsigned)((ln & 7) ^ ((((wv & 1) << 2) + (ln >> 4)) & 7)) * 16u;
+            const int row0 = m0 + wv * 8 + (ln >> 3);
+            auto va = [&](int i) { return (unsigned)min(row0 + 64 * i, p.M - 1) * (unsigned)(p.lda * 2) + ca16; };
+            if (part != 1) dma4<8192>(dst, rsA, soffa, va(0), va(1), va(2), va(3));
+            if (part != 2) {
+                dma2<8192>(dst + 4 * 8192, rsA, soffa, va(4), va(5));
+                const int cx = (ln & 31) ^ (((2 * (wv & 1) + (ln >> 5)) & 3) << 2);
+                const unsigned vx = (unsigned)(2 * wv + (ln >> 5)) * rowbytes + (unsigned)min(cx, cmax_t) * 16u, r16 = 16u * rowbytes;
+                dma4<8192>(dst + ASZ, rsX, soffx, vx, vx + r16, vx + 2 * r16, vx + 3 * r16);
+            }
+        } else {
+            if constexpr (NIA == 4) dma4<8192>(dst, rsA, soffa, voffa[0], voffa[1], voffa[2], voffa[3]);
+            else dma3<8192>(dst, rsA, soffa, voffa[0], voffa[1], voffa[2]);
+            dma4<8192>(dst + ASZ, rsX, soffx, voffx_t[0], voffx_t[1], voffx_t[2], voffx_t[3]);
+        }
     };
 
     f32x16 acc[TM][TN];
     auto compute = [&](int stage) {
         const unsigned char* sb = smem + stage * STAGE;
+        // 384-row tile: aoff[ks] = aoff[0] ^ 32 ks and xoff[1] = xoff[0] ^ 64 (the swizzles are XORs of bits that the row terms
+        // leave clear), taken per k-tile from opaque copies so that the six addresses are not kept in registers across the loop
+        int a0 = aoff[0], x0 = xoff[0];
+        if constexpr (WIDE) asm volatile("" : "+v"(a0), "+v"(x0));
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             bf16x8 af[TM], xf[TN];
+            const int ao = WIDE ? (a0 ^ (ks * 32)) : aoff[ks];
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(sb + aoff[ks] + i * 4096));
+            for (int i = 0; i < TM; ++i) af[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const s16x8*>(sb + ao + i * 4096));
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-                const unsigned char* q0 = sb + xoff[j] + ks * 16 * 512;
+                const unsigned char* q0 = sb + (WIDE ? (x0 ^ (j * 64)) : xoff[j]) + ks * 16 * 512;
                 const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(q0));
                 const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(q0 + 4 * 512));
                 const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -537,13 +581,16 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
         // books); at this point that drain coincides with the wait for the tile's first stage, in the epilogue it would
         // stall on the next tile's prefetch
         float bvr[TM];
+        auto fetch_bias = [&]() __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int mrow = cm0 + (wm * TM + i) * 32 + l31;
-            bvr[i] = (p.bias && mrow < p.M) ? p.bias[mrow] : 0.f;
-        }
+            for (int i = 0; i < TM; ++i) {
+                const int mrow = cm0 + (wm * TM + i) * 32 + l31;
+                bvr[i] = (p.bias && mrow < p.M) ? p.bias[mrow] : 0.f;
+            }
 #pragma unroll
-        for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(bvr[i]));
+            for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(bvr[i]));
+        };
+        if constexpr (!WIDE) fetch_bias();
         for (int kt = 0; kt < nk; ++kt) {
             if (kt == 0 || kt + 1 >= nk) wait_vmcnt<0>(); else wait_vmcnt<NI>();     // kt == 0 also drains the previous tile's stores
             __builtin_amdgcn_s_barrier();
@@ -552,15 +599,18 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
             __builtin_amdgcn_s_barrier();
             if (kt + 2 < nk) issue(kt + 2, kt & 1);
         }
+        // 384-row tile: no registers for the bias across the k-loop; here the last k-tile's wait has drained the counter and the
+        // next tile's requests have not been made, so the wait in front of the first use is for these loads alone
+        if constexpr (WIDE) fetch_bias();
         // next tile: its first two stages fly during this tile's epilogue.  With a fused multiplicand / residual the
         // epilogue has loads of its own, and the wait in front of their first use drains the whole counter (see above):
         // there the prefetch is issued in the last round, after those loads have been consumed
         const bool have_next = t + gridDim.x < ntiles;
-        const bool epi_loads = p.G || p.R;
+        const bool epi_loads = !WIDE && (p.G || p.R);
         if (have_next) setup_tile(t + gridDim.x);
         if (have_next && !epi_loads) {
-            issue(0, 0);                                  // (both stages are free: the k-loop ended with a barrier)
-            if (nk > 1) issue(1, 1);
+            issue(0, 0, WIDE ? 1 : 0);                    // (both stages are free: the k-loop ended with a barrier; 384-row tile: the
+            if (nk > 1) issue(1, 1);                      //  staging image is about to take the first 32 KB of stage 0)
         }
 
         // ---- epilogue: TM rounds of 64 channel rows (32 per wave row) through the staging image ----
@@ -580,8 +630,8 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
                 live[u4] = m < p.M && n < p.N;
                 off[u4] = plane + (long long)m * p.N + n;
                 gq[u4] = rq[u4] = make_uint4(0, 0, 0, 0);
-                if (live[u4] && p.G) gq[u4] = ld16(p.G + off[u4]);
-                if (live[u4] && p.R) rq[u4] = ld16(p.R + off[u4]);
+                if (!WIDE && live[u4] && p.G) gq[u4] = ld16(p.G + off[u4]);
+                if (!WIDE && live[u4] && p.R) rq[u4] = ld16(p.R + off[u4]);
             }
             // (b) accumulators (+ bias) -> bf16 -> staging image
             const float bv = bvr[i];
@@ -617,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
                 const uint4 raw = *reinterpret_cast<const uint4*>(stg + row * 512 + ((ch ^ (row & 15)) * 16));
                 if (live[u4]) {
                     const long long o = off[u4];
-                    if (!p.act && !p.G && !p.R) {
+                    if (WIDE || (!p.act && !p.G && !p.R)) {     // (the 384-row tile has no other epilogue)
                         mk_st16(p.Y + o, raw, p.nt);
                     } else {
                         if (p.act && p.Ypre) mk_st16(p.Ypre + o, raw, p.nt);
@@ -662,6 +712,7 @@ __global__ __launch_bounds__(512, 2) void conv_nn_ring_kernel(const ConvNN p, in
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                   // the staging image is free for the next round
         }
+        if (WIDE && have_next && !epi_loads) issue(0, 0, 2);      // ... and, 384-row tile, for the rest of the next tile's stage 0
     }
 #endif
 }
@@ -1824,8 +1875,10 @@ extern "C" int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, 
     MK_REQUIRE((lda % 8) == 0 && lda >= K, "conv1x1_nn: lda=%d must be a multiple of 8 and >= K=%d", lda, K);
     MK_REQUIRE((N % 8) == 0, "conv1x1_nn: pixel count %lld must be a multiple of 8", N);
     MK_REQUIRE((((uintptr_t)A | (uintptr_t)X) & 15) == 0, "conv1x1_nn: operands must be 16-byte aligned");
-    // MAKANI_AMD_CONV_NT (0 / 1: streaming output stores never / always) and MAKANI_AMD_ASTAT2 (see conv_nn_plan): unset = -1
-    static const int nt_env = env_int("MAKANI_AMD_CONV_NT"), astat2_env = env_int("MAKANI_AMD_ASTAT2");
+    // MAKANI_AMD_CONV_NT (0 / 1: streaming output stores never / always), MAKANI_AMD_ASTAT2 (see conv_nn_plan) and
+    // MAKANI_AMD_RING384 (0: never the 384-row tile of the ring kernel, see conv_nn_ring_rows): unset = -1
+    static const int nt_env = env_int("MAKANI_AMD_CONV_NT"), astat2_env = env_int("MAKANI_AMD_ASTAT2"),
+                     ring384_env = env_int("MAKANI_AMD_RING384");
     // streaming stores for outputs that fit the memory-side cache (256 MB) — see mk_st16
     const long long out_bytes = (long long)B * M * N * 2;          // per output tensor (with the pre-activation there are two)
     const int nt = nt_env == 0 ? 0 : (nt_env == 1 ? 1 : out_bytes <= (256ll << 20));
@@ -1872,13 +1925,13 @@ extern "C" int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, 
         break;
     }
     case ConvNnKernel::ring: {
-        const bool big = (M % 256 == 0) || M > 576;
-        const int bm = big ? 256 : 192;
+        const int bm = conv_nn_ring_rows(M, K, B, N, act || Ypre || R || G, ring384_env);
         const int tm = (M + bm - 1) / bm;
         const long long tn = (N + 255) / 256;
         const long long nt = (long long)tm * tn * B;
         const unsigned grid = (unsigned)(nt < 256 ? nt : 256);
-        if (big) hipLaunchKernelGGL((conv_nn_ring_kernel<4>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
+        if (bm == 384) hipLaunchKernelGGL((conv_nn_ring_kernel<6>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
+        else if (bm == 256) hipLaunchKernelGGL((conv_nn_ring_kernel<4>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
         else hipLaunchKernelGGL((conv_nn_ring_kernel<3>), dim3(grid), dim3(512), 0, s, p, tm, tn, nt);
         break;
     }

@@ -27,3 +27,19 @@ inline ConvNnKernel conv_nn_plan(int M, int K, int lda, int B, long long N, bool
     if (K >= 64 && M >= 192 && N * 2 * 64 < (1ll << 31) && (long long)M * lda * 2 < (1ll << 31) && N >= 256) return ConvNnKernel::ring;
     return ConvNnKernel::tile;
 }
+
+// Tile height of the ring kernel (output channels per tile; the tile is 256 pixels wide): 256 where M is made of whole 256-row tiles
+// or is large, else 192 — and ONE 384-row tile where that would be two of 192 under a long contraction (384 <- 768, the MLP's second
+// layer and the data gradient of its first).  Per 256 pixels the two 192-row tiles ingest 2 x (192 x K weights + K x 256 activations),
+// the 384-row tile 384 x K + K x 256: 10 bytes per output element instead of 14, and the memory path of the CU is what bounds the
+// kernel (docs/LAB_NOTEBOOK.md 6.12).  The 384-row tile has 192 accumulator registers per lane: it exists
+// without epilogue operands only (has_epilogue: activation, stored pre-activation, residual or gelu' operand; a bias is none), and
+// it halves the tile count, so it needs as many tiles as the persistent grid has workgroups (256) — the shards of one rank keep
+// two tiles.  K = 384 stays with 192 rows: full grids of it run weight-stationary, only shards reach the ring kernel.
+// ring384_env: MAKANI_AMD_RING384 (negative = unset; 0 = never the 384-row tile, for A/B runs).
+inline int conv_nn_ring_rows(int M, int K, int B, long long N, bool has_epilogue, int ring384_env) {
+    const int rows = ((M % 256 == 0) || M > 576) ? 256 : 192;
+    const long long tiles384 = ((N + 255) / 256) * B;
+    if (rows == 192 && M > 192 && M <= 384 && K >= 512 && !has_epilogue && tiles384 >= 256 && ring384_env != 0) return 384;
+    return rows;
+}
