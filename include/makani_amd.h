@@ -495,6 +495,19 @@ int mk_metric_ens_sums(const void* f, int f_dtype, const float* obs, const float
 int mk_noise_update(float* state, const float* xi, const float* sigma, const float* phi, const long long* rng, int mode, int B,
                     int T, int C, int L, int M, int reflect, void* stream);
 int mk_noise_advance(long long* rng, long long n, void* stream);
+/* The same update on a BOX of the state, for a sphere split over h x w ranks.  One time level of the GLOBAL array is (B, C, R, S)
+ * floats (spectral processes: R = lmax, S = 2 mmax; DummyNoiseS2: R = nlat, S = nlon); this call owns rows [r0, r0 + Rl) and
+ * floats [s0, s0 + Sl) of every (batch entry, channel) plane.  state: the local contiguous (B, T, C, Rl, Sl); sigma: (C, Rl), the
+ * local slice; phi: (C); xi, when given, shard-shaped like state ((B, 1, C, Rl, Sl) for MK_NOISE_AR) and used as it is.
+ * Counter contract: the element with flat index e in the global level (B, C, R, S) takes normal e & 3 of Philox group e >> 2 at
+ *   (seed, offset + t).  A box therefore holds the numbers the whole array holds at those positions, whatever the tiling; with
+ *   the box equal to the whole array this is mk_noise_update (which calls it).  Groups that straddle a row end or a box edge are
+ *   evaluated by every thread that owns one of their lanes; lanes outside the box are neither loaded nor stored.
+ * C R S < 2^31.  16-byte accesses when all strides and offsets, global and local, are multiples of 4 floats; 8-byte accesses when
+ *   they are even (a spectral (re, im) pair never leaves its group), 16-byte ones for the groups that are whole and locally
+ *   aligned; element-wise masks otherwise. */
+int mk_noise_update_shard(float* state, const float* xi, const float* sigma, const float* phi, const long long* rng, int mode,
+                          int B, int T, int C, int R, int S, int r0, int Rl, int s0, int Sl, int reflect, void* stream);
 
 /* ---- DISCO convolution and S2 resampling (FourCastNet3's local operators) ----------------------------------------
  * Replace th.DiscreteContinuousConvS2's sparse contraction and th.ResampleS2 [torch-harmonics, un-vendored; call sites

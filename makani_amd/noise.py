@@ -14,7 +14,11 @@ with it.  What differs:
   ``get_rng_state()`` returns ``(None, rng.cpu().clone())`` and ``set_rng_state(cpu_state, gpu_state)`` restores from
   ``gpu_state``.  The stream of normals is this package's own, not torch's.
 * ``forward`` is the package's ``InverseRealSHT`` on ``view_as_complex(state)`` (no copy).
-* serial only: a spatial (h x w) group larger than one raises ``NotImplementedError``.
+* on a sphere split over h x w ranks (``comm.get_size("spatial") > 1`` with the ``h`` / ``w`` groups behind it) the spectral
+  state is split over h (degree l) and w (order m) as in the reference and ``forward`` is ``DistributedInverseRealSHT``, but the
+  counter of every element is its GLOBAL index (``mk_noise_update_shard``): ranks that share a seed
+  (``noise_seed_reflect(..., share_over_model=True)``) hold exactly the slices of the serial state, whatever the layout.
+  A spatial group without h / w groups behind it raises ``NotImplementedError`` ("serial only").
 * construction and the buffer mathematics work on the CPU; ``update`` / ``forward`` need the module on a GPU.
 """
 import math
@@ -35,17 +39,28 @@ class BaseNoiseS2(nn.Module):
     def __init__(self, img_shape, batch_size, num_channels, num_time_steps, grid_type="equiangular", lmax=None, seed=333,
                  reflect=False, **kwargs):
         super().__init__()
-        if comm.get_size("spatial") > 1:
-            raise NotImplementedError("noise on a spatially split sphere (h x w > 1) needs the distributed inverse SHT: "
-                                      "the HIP noise processes are serial only")
         self.nlat, self.nlon = img_shape
         self.num_channels = num_channels
         self.num_time_steps = num_time_steps
         self.reflect = reflect
-        self.isht = InverseRealSHT(self.nlat, self.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
-        self.lmax = self.lmax_local = self.isht.lmax
-        self.mmax = self.mmax_local = self.isht.mmax
-        self.nlat_local, self.nlon_local = self.nlat, self.nlon
+        self.spatial_parallel = comm.get_size("spatial") > 1
+        if self.spatial_parallel:
+            from . import distributed as thd
+            if comm.get_size("h") * comm.get_size("w") != comm.get_size("spatial") or not thd.ensure_initialized():
+                raise NotImplementedError("noise on a spatially split sphere needs the h / w groups of the distributed inverse SHT "
+                                          "behind the spatial group: without them the HIP noise processes are serial only")
+            self.isht = isht = thd.DistributedInverseRealSHT(self.nlat, self.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+            ih, iw = isht.comm_rank_polar, isht.comm_rank_azimuth
+            self.lmax_local, self.mmax_local = isht.l_shapes[ih], isht.m_shapes[iw]
+            self.nlat_local, self.nlon_local = isht.lat_shapes[ih], isht.lon_shapes[iw]
+            self.l_off, self.m_off = isht.l_off, isht.m_off
+            self.lat_off, self.lon_off = sum(isht.lat_shapes[:ih]), sum(isht.lon_shapes[:iw])
+        else:
+            self.isht = InverseRealSHT(self.nlat, self.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+            self.lmax_local, self.mmax_local = self.isht.lmax, self.isht.mmax
+            self.nlat_local, self.nlon_local = self.nlat, self.nlon
+            self.l_off = self.m_off = self.lat_off = self.lon_off = 0
+        self.lmax, self.mmax = self.isht.lmax, self.isht.mmax
         self.set_rng(seed=seed)
         self._ensure_state(batch_size, device=torch.device("cpu"), dtype=torch.float32)
 
@@ -110,18 +125,20 @@ class BaseNoiseS2(nn.Module):
             self.rng.copy_(torch.as_tensor(gpu_state, dtype=torch.int64).reshape(2))
 
     # ---- update -------------------------------------------------------------------------------------------------
-    def _kernel_dims(self):
-        """(C, L, M) of one time level as the kernel counts it: C L M 2 floats in the reference's memory order"""
-        return self.num_channels, self.lmax_local, self.mmax_local
+    def _kernel_box(self):
+        """(R, S, r0, Rl, s0, Sl): one (batch entry, channel) plane of the GLOBAL time level as the kernel counts it, R rows of
+        S floats in the reference's memory order, and this rank's rows [r0, r0 + Rl) and floats [s0, s0 + Sl) of it"""
+        return self.lmax, 2 * self.mmax, self.l_off, self.lmax_local, 2 * self.m_off, 2 * self.mmax_local
 
     def _launch(self, mode, innovation=None, sigma=None, phi=None):
-        """one pass over ``state`` (mk_noise_update), then the counter moves on by the time levels drawn"""
+        """one pass over ``state`` (mk_noise_update, on a split sphere mk_noise_update_shard), then the counter moves on by the
+        time levels drawn"""
         self._require_gpu()
         state = self.state
         if state.dtype != torch.float32 or not state.is_contiguous():
             raise TypeError(f"the noise state has to be contiguous float32, got {state.dtype}")
-        B, T = state.shape[0], self.num_time_steps
-        C, L, M = self._kernel_dims()
+        B, T, C = state.shape[0], self.num_time_steps, self.num_channels
+        R, S, r0, Rl, s0, Sl = self._kernel_box()
         levels = 1 if mode == MODE_AR else T
         xi = None
         if innovation is not None:
@@ -131,8 +148,12 @@ class BaseNoiseS2(nn.Module):
             xi = innovation.detach().to(device=state.device, dtype=torch.float32).contiguous()
         with torch.cuda.device(state.device):
             L_ = _lib.lib()
-            _lib.check(L_.mk_noise_update(_lib.ptr(state), _lib.ptr(xi), _lib.ptr(sigma), _lib.ptr(phi), _lib.ptr(self.rng), mode,
-                                          B, T, C, L, M, int(bool(self.reflect)), _lib.stream()), "mk_noise_update")
+            args = (_lib.ptr(state), _lib.ptr(xi), _lib.ptr(sigma), _lib.ptr(phi), _lib.ptr(self.rng), mode, B, T, C)
+            if self.spatial_parallel:
+                _lib.check(L_.mk_noise_update_shard(*args, R, S, r0, Rl, s0, Sl, int(bool(self.reflect)), _lib.stream()),
+                           "mk_noise_update_shard")
+            else:
+                _lib.check(L_.mk_noise_update(*args, R, S // 2, int(bool(self.reflect)), _lib.stream()), "mk_noise_update")
             if xi is None:
                 _lib.check(L_.mk_noise_advance(_lib.ptr(self.rng), levels, _lib.stream()), "mk_noise_advance")
 
@@ -159,7 +180,8 @@ class BaseNoiseS2(nn.Module):
 class IsotropicGaussianRandomFieldS2(BaseNoiseS2):
     """Stateless isotropic Gaussian field with the power-law spectrum ``sigma_l ~ (2l + 1)^(-alpha / 2)``, normalised to the
     pointwise variance ``sigma^2`` (Lang & Schwab 2015).  ``sigma_l`` (1, 1, 1, L, M), zero for m > l, is applied in
-    ``forward`` with torch operations: with ``learnable=True`` it is a parameter and autograd gives its gradient."""
+    ``forward`` with torch operations: with ``learnable=True`` it is a parameter and autograd gives its gradient.  On a split
+    sphere ``sigma_l`` is this rank's (l, m) slice."""
 
     def __init__(self, img_shape, batch_size, num_channels, num_time_steps=1, sigma=1.0, alpha=0.0, grid_type="equiangular",
                  lmax=None, seed=333, reflect=False, learnable=False, **kwargs):
@@ -172,6 +194,7 @@ class IsotropicGaussianRandomFieldS2(BaseNoiseS2):
         norm = torch.sum((2 * degree + 1) * spectrum / 4.0 / math.pi)
         sigma_l = torch.where(order <= degree, sigma * torch.sqrt(spectrum / norm), 0.0)
         sigma_l = sigma_l.reshape(1, 1, 1, self.lmax, self.mmax).to(dtype=torch.float32)
+        sigma_l = sigma_l[..., self.l_off:self.l_off + self.lmax_local, self.m_off:self.m_off + self.mmax_local].contiguous()
         if learnable:
             self.register_parameter("sigma_l", nn.Parameter(sigma_l))
             self.sigma_l.sharded_dims_mp = [None, None, None, "h", "w"]
@@ -226,6 +249,7 @@ class DiffusionNoiseS2(BaseNoiseS2):
         sigma_l = math.sqrt(4 * math.pi) * (amp * torch.exp(-0.5 * kT * degree * (degree + 1)))
         phi = phi.reshape(C, 1, 1, 1).to(dtype=torch.float32)                          # (C, L, M, 2) broadcast
         sigma_l = sigma_l.reshape(1, 1, C, self.lmax, 1, 1).to(dtype=torch.float32)    # (B, T, C, L, M, 2) broadcast
+        sigma_l = sigma_l[:, :, :, self.l_off:self.l_off + self.lmax_local].contiguous()     # this rank's degrees
         if learnable:
             self.phi = nn.Parameter(phi)
             self.phi.is_shared_mp = ["matmul", "h", "w"]
@@ -272,7 +296,8 @@ class DiffusionNoiseS2(BaseNoiseS2):
 class DummyNoiseS2(BaseNoiseS2):
     """Noise of the right shape without a transform, for tests of shapes and control flow: the state lives on the grid,
     ``(B, T, C, nlat, nlon)``, and ``forward`` returns it (the live buffer, as the reference does).  ``constant_zero`` keeps
-    zeros, ``constant_random`` redraws standard normals with every ``update``."""
+    zeros, ``constant_random`` redraws standard normals with every ``update``.  On a split sphere the state is the rank's
+    latitude / longitude slice of the serial one."""
 
     def __init__(self, img_shape, batch_size, num_channels, num_time_steps=1, mode="constant_zero", seed=333, **kwargs):
         if mode not in ("constant_zero", "constant_random"):
@@ -285,10 +310,10 @@ class DummyNoiseS2(BaseNoiseS2):
     def _state_shape_suffix(self):
         return (self.num_time_steps, self.num_channels, self.nlat_local, self.nlon_local)
 
-    def _kernel_dims(self):
-        if self.nlon_local % 2:
+    def _kernel_box(self):
+        if self.nlon % 2:
             raise NotImplementedError("DummyNoiseS2 'constant_random' needs an even number of longitudes")
-        return self.num_channels, self.nlat_local, self.nlon_local // 2
+        return self.nlat, self.nlon, self.lat_off, self.nlat_local, self.lon_off, self.nlon_local
 
     def is_stateful(self):
         return False
@@ -314,14 +339,17 @@ class DummyNoiseS2(BaseNoiseS2):
         return state
 
 
-def noise_seed_reflect(centered: bool, seed_offset: int = 0):
+def noise_seed_reflect(centered: bool, seed_offset: int = 0, *, share_over_model: bool = False):
     """Per-rank base seed and reflection flag of a noise source.  Not centered: every (model rank, data rank) has its own
-    seed.  Centered: the ensemble ranks (0, 1), (2, 3), ... share a seed and differ by the sign of every draw."""
+    seed.  Centered: the ensemble ranks (0, 1), (2, 3), ... share a seed and differ by the sign of every draw.
+    ``share_over_model``: the model rank enters as 0, so the h x w ranks of one model instance share a stream and, the counter
+    being global, hold the shards of ONE field — the serial one; the default is the reference's seed per model rank."""
     nmodel = comm.get_size("model")
+    rank_m = 0 if share_over_model else comm.get_rank("model")
     if not centered:
-        return 333 + seed_offset + comm.get_rank("model") + nmodel * comm.get_rank("data"), False
+        return 333 + seed_offset + rank_m + nmodel * comm.get_rank("data"), False
     rank_e = comm.get_rank("ensemble")
-    seed = 333 + seed_offset + comm.get_rank("model") + nmodel * (rank_e // 2) + nmodel * comm.get_size("ensemble") * comm.get_rank("batch")
+    seed = 333 + seed_offset + rank_m + nmodel * (rank_e // 2) + nmodel * comm.get_size("ensemble") * comm.get_rank("batch")
     return seed, rank_e % 2 == 0
 
 
@@ -363,6 +391,34 @@ class InputNoise(nn.Module):
         self.input_noise_mode = mode
         self.perturb_channels = None if perturb_channels is None else [int(c) for c in perturb_channels]
         self.n_history = int(n_history)
+
+    @classmethod
+    def from_params(cls, params, share_over_model=True):
+        """The stage ``Preprocessor2D.__init__`` builds from ``params.input_noise`` (``preprocessor.py:149-232``): ``type``,
+        ``mode``, ``n_channels`` / ``perturb_channels`` (names looked up in ``params.channel_names``), ``centered``, ``lmax``,
+        ``sigma``, ``kT``, ``alpha``, ``learnable``, ``lambd`` (default ``params.dt * params.dhours / 6``); the grid is
+        ``(img_shape_x_resampled, img_shape_y_resampled)`` on ``model_grid_type``, the history ``n_history``, the batch
+        ``batch_size``.  ``share_over_model``: see ``noise_seed_reflect`` (``False`` gives the reference's seeds)."""
+        cfg = params.get("input_noise", None)
+        if cfg is None:
+            raise ValueError("params.input_noise is not set")
+        if "type" not in cfg:
+            raise ValueError("Error, please specify an input noise type")
+        mode = cfg.get("mode", "concatenate")
+        perturb = None
+        if mode == "concatenate":
+            channels = cfg.get("n_channels", 1)
+        elif mode == "perturb":
+            perturb = [params.channel_names.index(ch) for ch in cfg.get("perturb_channels", params.channel_names)]
+            channels = len(perturb)
+        else:
+            raise NotImplementedError(f"Error, input noise mode {mode} not supported.")
+        seed, reflect = noise_seed_reflect(cfg.get("centered", False), share_over_model=share_over_model)
+        lambd = {"default_lambd": params.dt * params.dhours / 6.0} if cfg["type"] == "diffusion" and "lambd" not in cfg else {}
+        noise = build_noise(cfg, img_shape=(params.img_shape_x_resampled, params.img_shape_y_resampled),
+                            batch_size=params.batch_size, num_channels=channels, num_time_steps=params.n_history + 1,
+                            grid_type=params.model_grid_type, seed=seed, reflect=reflect, **lambd)
+        return cls(noise, mode=mode, perturb_channels=perturb, n_history=params.n_history)
 
     def forward(self, x, xc=None):
         flat = x.dim() == 4

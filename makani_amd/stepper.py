@@ -4,7 +4,8 @@
 makani's wrapper threads every step through ``Preprocessor2D`` (history normalisation, unpredicted / static feature
 channels, input noise, bias correction — the data pipeline, SURVEY §2: OUT).  In the north-star configuration all
 of those stages are identities (``history_normalization_mode: "none"``, no zenith / orography / land-mask channels,
-no noise), and what remains is the part that decides the cost of a rollout on the GPU:
+no noise), and what remains is the part that decides the cost of a rollout on the GPU, plus the one stage the ensemble
+recipes cannot do without — the input noise (``input_noise=``, a ``makani_amd.noise.InputNoise``):
 
 * the loop itself — ``n_future + 1`` network calls, the prediction of step k appended to the history window that
   feeds step k+1 (``stepper.py:236-281``, ``preprocessor.py:341-410``), all steps concatenated along the channel axis
@@ -17,8 +18,13 @@ no noise), and what remains is the part that decides the cost of a rollout on th
   checkpointing — on 288 GB of HBM the plain rollout is the faster default, checkpointing buys batch size.
   The HIP autograd functions hold no private RNG state and write their saved tensors only once, so recomputation is
   bit-identical to the first forward (``tests/test_gpu_model.py::test_rollout_checkpointing_is_exact_and_matches_manual_unroll``).
+* **input noise** — with ``update_state`` the process is advanced once before the loop (``replace_state`` decides between a
+  fresh stationary state and one autoregressive step) and by one autoregressive step between two steps of the rollout; every
+  step's network input is ``input_noise(window)`` while the history window itself stays un-noised (``stepper.py:229-279``).
+  The noise call sits outside the checkpointed network call: a recompute draws nothing.
 
-Evaluation mode performs ONE step (``stepper.py:286-313``): inference drives the rollout itself.
+Evaluation mode performs ONE step (``stepper.py:286-313``): inference drives the rollout itself; the noise state is sized to
+the call's batch there.
 """
 import torch
 import torch.nn as nn
@@ -34,14 +40,14 @@ def _private_generators(module):
 
 
 class MultiStepWrapper(nn.Module):
-    """``MultiStepWrapper(model, n_future=, n_history=, push_forward=, multistep_checkpoint=)`` or, with makani's own
-    calling convention, ``MultiStepWrapper.from_params(params, model_handle)`` (``model_registry.py:257-262``).
+    """``MultiStepWrapper(model, n_future=, n_history=, push_forward=, multistep_checkpoint=, input_noise=)`` or, with
+    makani's own calling convention, ``MultiStepWrapper.from_params(params, model_handle)`` (``model_registry.py:257-262``).
 
     ``forward(inp)``: ``inp`` (B, (n_history + 1)·C, H, W) → (B, (n_future + 1)·C_out, H, W) in training mode,
-    (B, C_out, H, W) in evaluation mode.  ``update_state`` / ``replace_state`` are accepted for signature
-    compatibility; there is no stochastic state to advance here."""
+    (B, C_out, H, W) in evaluation mode.  ``update_state`` / ``replace_state`` steer the state of ``input_noise`` (an
+    ``InputNoise``, e.g. ``InputNoise.from_params(params)``); without one they are accepted for signature compatibility."""
 
-    def __init__(self, model, n_future=0, n_history=0, push_forward=False, multistep_checkpoint=False):
+    def __init__(self, model, n_future=0, n_history=0, push_forward=False, multistep_checkpoint=False, input_noise=None):
         super().__init__()
         if n_future < 0 or n_history < 0:
             raise ValueError(f"n_future ({n_future}) and n_history ({n_history}) must be >= 0")
@@ -49,6 +55,9 @@ class MultiStepWrapper(nn.Module):
         self.n_future, self.n_history = int(n_future), int(n_history)
         self.push_forward_mode = bool(push_forward)
         self.multistep_checkpoint = bool(multistep_checkpoint)
+        if input_noise is not None and input_noise.n_history != self.n_history:
+            raise ValueError(f"input_noise carries n_history = {input_noise.n_history}, the rollout {self.n_history}")
+        self.input_noise = input_noise
         if self.multistep_checkpoint:
             offenders = _private_generators(model)
             if offenders:
@@ -64,9 +73,11 @@ class MultiStepWrapper(nn.Module):
         mode = get("history_normalization_mode", "none")
         if mode != "none":
             raise NotImplementedError(f"history_normalization_mode {mode!r}: only 'none' (the preprocessor is out of scope)")
-        for key in ("input_noise", "bias_correction"):
-            if get(key, None) is not None:
-                raise NotImplementedError(f"params.{key} is set: that preprocessor stage is out of scope here")
+        if get("input_noise", None) is not None:
+            raise NotImplementedError("params.input_noise is set: from_params does not build the noise stage — build it with "
+                                      "InputNoise.from_params(params) and hand it to the constructor's input_noise= keyword")
+        if get("bias_correction", None) is not None:
+            raise NotImplementedError("params.bias_correction is set: that preprocessor stage is out of scope here")
         for key in ("add_zenith", "add_orography", "add_landmask", "add_soiltype", "add_copernicus_emb"):
             if get(key, False):
                 raise NotImplementedError(f"params.{key}: unpredicted / static feature channels are out of scope here")
@@ -94,31 +105,49 @@ class MultiStepWrapper(nn.Module):
         return self.model(x)
 
     def forward(self, inp, update_state=True, replace_state=True):
+        noise = self.input_noise
         if not self.training:
-            return self.model(inp)
+            if noise is None:
+                return self.model(inp)
+            if update_state:
+                noise.update_internal_state(replace_state=replace_state, batch_size=inp.shape[0])
+            return self.model(noise(inp))
+        if noise is not None and update_state:
+            noise.update_internal_state(replace_state=replace_state)
         result = []
         window = inp
         for step in range(self.n_future + 1):
             if self.push_forward_mode:
                 window = window.detach()
-            pred = self._step(window)
+            pred = self._step(window if noise is None else noise(window))       # (the noise is drawn outside the checkpoint)
             result.append(pred)
             if step < self.n_future:
+                if noise is not None:
+                    noise.update_internal_state(replace_state=False)
                 window = self.append_history(window, pred)
         return torch.cat(result, dim=1) if len(result) > 1 else result[0]
 
 
 class SingleStepWrapper(nn.Module):
-    """one step; ``encode_process`` forwarded when the network has it (``stepper.py:50-173``)"""
+    """one step; ``encode_process`` forwarded when the network has it (``stepper.py:50-173``).  With ``input_noise`` (an
+    ``InputNoise``) the state is advanced at the call's batch size when ``update_state`` says so, then appended / added."""
 
-    def __init__(self, model):
+    def __init__(self, model, input_noise=None):
         super().__init__()
         self.model = model
+        self.input_noise = input_noise
+
+    def _preprocess(self, inp, update_state, replace_state):
+        if self.input_noise is None:
+            return inp
+        if update_state:
+            self.input_noise.update_internal_state(replace_state=replace_state, batch_size=inp.shape[0])
+        return self.input_noise(inp)
 
     def forward(self, inp, update_state=True, replace_state=True):
-        return self.model(inp)
+        return self.model(self._preprocess(inp, update_state, replace_state))
 
     def encode_process(self, inp, update_state=True, replace_state=True):
         if not hasattr(self.model, "encode_process"):
             raise NotImplementedError(f"{type(self.model).__name__} does not expose encode_process().")
-        return self.model.encode_process(inp)
+        return self.model.encode_process(self._preprocess(inp, update_state, replace_state))

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [losses] [metrics]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -518,6 +518,44 @@ def noise():
         print(f"noise B={B:2d}: replace {tr:7.3f} ms | forward (inverse SHT of {B * T * C} planes) {tf:7.3f} ms = "
               f"{tf / (tk + tf) * 100:5.1f} % of update + forward", flush=True)
         del m, st, twin, dst
+
+
+def noise_shard():
+    """mk_noise_update_shard at the boxes one rank of BASELINE configs[3] / [4] owns (721 x 1440, lmax = mmax = 721, 8 channels,
+    B = 2, T = 1, the autoregressive rule; l split [361, 360] under h = 2 and [181, 180, 180, 180] under h = 4, m split
+    [361, 360]) beside mk_noise_update on a whole array of the same number of elements; traffic counted as one read and one write
+    of the state.  Seven rounds, the two timed in turn within each; min / median / max over the rounds."""
+    from makani_amd import _lib
+    L_ = _lib.lib()
+    B, T, C, lmax, mmax = 2, 1, 8, 721, 721
+    rng = torch.tensor([333, 0], dtype=torch.int64, device=dev)
+    phi = torch.full((C,), 0.8, device=dev)
+    for name, (r0, Rl), (m0, ml) in (("h2 w2 rank (0, 0)", (0, 361), (0, 361)), ("h2 w2 rank (0, 1)", (0, 361), (361, 360)),
+                                     ("h2 w2 rank (1, 0)", (361, 360), (0, 361)), ("h2 w2 rank (1, 1)", (361, 360), (361, 360)),
+                                     ("h4 w2 rank (0, 0)", (0, 181), (0, 361)), ("h4 w2 rank (0, 1)", (0, 181), (361, 360)),
+                                     ("h4 w2 rank (3, 0)", (541, 180), (0, 361)), ("h4 w2 rank (3, 1)", (541, 180), (361, 360))):
+        box, whole = torch.randn(B, T, C, Rl, ml, 2, device=dev), torch.randn(B, T, C, Rl, ml, 2, device=dev)
+        sigma = torch.rand(C, Rl, device=dev) * 0.1
+        nbytes = 2 * box.numel() * 4
+        head = (_lib.ptr(sigma), _lib.ptr(phi), _lib.ptr(rng), 1, B, T, C)
+
+        def shard():
+            _lib.check(L_.mk_noise_update_shard(_lib.ptr(box), None, *head, lmax, 2 * mmax, r0, Rl, 2 * m0, 2 * ml, 0, _lib.stream()))
+
+        def serial():
+            _lib.check(L_.mk_noise_update(_lib.ptr(whole), None, *head, Rl, ml, 0, _lib.stream()))
+
+        ts, tw = [], []
+        for _ in range(7):
+            ts.append(timeit(shard, reps=200, warm=5))
+            tw.append(timeit(serial, reps=200, warm=5))
+        ts.sort()
+        tw.sort()
+        print(f"noise shard {name}: rows [{r0}, {r0 + Rl}) x orders [{m0}, {m0 + ml}) ({nbytes / 2e6:.1f} MB state) | shard "
+              f"{ts[0] * 1e3:6.1f} / {ts[3] * 1e3:6.1f} / {ts[6] * 1e3:6.1f} us = {nbytes / ts[3] / 1e6:7.1f} GB/s | whole array of the "
+              f"same size {tw[0] * 1e3:6.1f} / {tw[3] * 1e3:6.1f} / {tw[6] * 1e3:6.1f} us = {nbytes / tw[3] / 1e6:7.1f} GB/s | "
+              f"shard / whole {ts[3] / tw[3]:5.2f}", flush=True)
+        del box, whole
 
 
 if __name__ == "__main__":
