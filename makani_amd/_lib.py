@@ -206,6 +206,20 @@ def ptr(t):
     return c_vp(t.data_ptr())
 
 
+def need_gpu(t, what="losses"):
+    if not t.is_cuda:
+        raise RuntimeError(f"makani_amd {what} run on the GPU (HIP) path only")
+
+
+def prep(t, ref_shape=None):
+    """``t`` as a contiguous f32 | bf16 tensor (other dtypes: cast to f32), expanded to ``ref_shape`` when that is given"""
+    if t.dtype not in (torch.float32, torch.bfloat16):
+        t = t.float()
+    if ref_shape is not None and tuple(t.shape) != tuple(ref_shape):
+        t = t.expand(ref_shape)
+    return t.contiguous()
+
+
 def dtype_code(t):
     if t.dtype == torch.float32:
         return MK_F32

@@ -15,7 +15,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, legendre
-from ._lib import device_guard, check, dtype_code, lib, ptr, stream
+from ._lib import device_guard, check, dtype_code, lib, need_gpu, prep, ptr, stream
+from .ensemble import MAX_ENSEMBLE          # noqa: F401  (importable from here as before)
+from .ensemble import (ReduceFromGroupFn, check_forecast_dims, check_weight_dims, ensemble_active, ensemble_size_check,
+                       ensemble_split, flatten_and_split)
 
 GRID_TO_QUADRATURE_RULE = {
     "euclidean": "uniform",
@@ -46,24 +49,15 @@ def _quad_launch(a, b, wgt, q, mode, p):
     return sums[0]
 
 
-def _prep(t, ref_shape=None):
-    if t.dtype not in (torch.float32, torch.bfloat16):
-        t = t.float()
-    if ref_shape is not None and tuple(t.shape) != tuple(ref_shape):
-        t = t.expand(ref_shape)
-    return t.contiguous()
-
-
 class QuadLpFn(torch.autograd.Function):
     """out[...] = sum_{h,w} q[h,w] * (mode ? |a - b|^p : a) * wgt;  a, b: (..., H, W)."""
 
     @staticmethod
     def forward(ctx, a, b, wgt, q, mode, p):
-        if not a.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
-        a = _prep(a)
-        b = _prep(b, a.shape) if b is not None else None
-        w = _prep(wgt, a.shape).float() if wgt is not None else None
+        need_gpu(a)
+        a = prep(a)
+        b = prep(b, a.shape) if b is not None else None
+        w = prep(wgt, a.shape).float() if wgt is not None else None
         ctx.save_for_backward(a, b, w, q)
         ctx.meta = (mode, float(p))
         return _quad_launch(a, b, w, q, mode, p).view(a.shape[:-2])
@@ -235,8 +229,7 @@ class SpectralLpLoss(nn.Module):
         """sum_{l,m} w(m) |sht(x)|^p per (b, c)"""
         if x.dim() != 4:
             raise ValueError(f"expected (B, C, H, W), got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        need_gpu(x)
         B, C = x.shape[:2]
         if x.dtype not in (torch.float32, torch.bfloat16):
             x = x.float()
@@ -345,7 +338,6 @@ class GeometricLpLoss(nn.Module):
 # ensemble CRPS (makani/utils/losses/crps_loss.py:277-452)
 # --------------------------------------------------------------------------- #
 _CRPS_TYPES = {"skillspread": 0, "probability weighted moment": 1, "naive skillspread": 2, "gauss": 3, "cdf": 4}
-MAX_ENSEMBLE = 32          # members of a grid point live in registers (csrc/crps.hip)
 
 
 class CrpsFn(torch.autograd.Function):
@@ -354,11 +346,9 @@ class CrpsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, forecasts, obs, q, wgt, ctype, alpha, eps, ens_w=None):
         B, E, Cc, H, W = forecasts.shape
-        if E > MAX_ENSEMBLE:
-            raise NotImplementedError(f"ensemble size {E}: the HIP CRPS kernels hold the members of a point in registers "
-                                      f"(2 <= E <= {MAX_ENSEMBLE})")
+        ensemble_size_check(E, "CRPS")
         hw = H * W
-        f, o = _prep(forecasts), _prep(obs)
+        f, o = prep(forecasts), prep(obs)
         w = wgt.float().contiguous() if wgt is not None else None
         ch = lib().mk_crps_chunks(hw)
         partial = torch.empty((B * Cc, ch), dtype=torch.float32, device=f.device)
@@ -388,9 +378,7 @@ class CrpsComplexFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, forecasts, obs, q, wgt, alpha):
         B, E, Cc, H, W = forecasts.shape
-        if E > MAX_ENSEMBLE:
-            raise NotImplementedError(f"ensemble size {E}: the HIP CRPS kernels hold the members of a point in registers "
-                                      f"(2 <= E <= {MAX_ENSEMBLE})")
+        ensemble_size_check(E, "CRPS")
         hw = H * W
         f = torch.view_as_real(forecasts.to(torch.complex64).contiguous())
         o = torch.view_as_real(obs.to(torch.complex64).contiguous())
@@ -415,87 +403,6 @@ class CrpsComplexFn(torch.autograd.Function):
         return torch.view_as_complex(gf), None, None, None, None
 
 
-class _EnsembleTransposeFn(torch.autograd.Function):
-    """``distributed_transpose(forecasts, (-1, 0), ensemble_shapes, "ensemble")`` of ``crps_loss.py:362-366,566-570``: every
-    rank of the ensemble group holds E_loc members on all N points and ends up with ALL members on its share of the points
-    (``compute_split_shapes(N, n)``).  x (B, E_loc, C, N) -> (B, E_loc * n, C, N_loc); backward is the reverse exchange."""
-
-    @staticmethod
-    def forward(ctx, x, group):
-        import torch.distributed as dist
-        from . import distributed as thd
-        n, me = dist.get_world_size(group), dist.get_rank(group)
-        B, El, Cc, N = x.shape
-        sizes = thd.compute_split_shapes(N, n)
-        off = [0]
-        for v in sizes:
-            off.append(off[-1] + v)
-        send = [x[..., off[r]:off[r + 1]].contiguous() for r in range(n)]
-        recv = [torch.empty((B, El, Cc, sizes[me]), dtype=x.dtype, device=x.device) for _ in range(n)]
-        thd._exchange(recv, send, group)
-        ctx.meta = (group, n, me, sizes, off, N)
-        return torch.cat(recv, dim=1)
-
-    @staticmethod
-    def backward(ctx, g):
-        from . import distributed as thd
-        group, n, me, sizes, off, N = ctx.meta
-        B, E, Cc, Nl = g.shape
-        El = E // n
-        send = [g[:, r * El:(r + 1) * El].contiguous() for r in range(n)]
-        recv = [torch.empty((B, El, Cc, sizes[r]), dtype=g.dtype, device=g.device) for r in range(n)]
-        thd._exchange(recv, send, group)
-        return torch.cat(recv, dim=3), None
-
-
-def _ensemble_split(forecasts, obs, q, wgt):
-    """the ensemble-parallel path of the CRPS losses: (forecasts with ALL members on this rank's share of the points, that
-    share of the observations / quadrature weights / spatial weights, the group).  forecasts (B, E_loc, C, N) etc."""
-    import torch.distributed as dist
-    from . import comm as _comm
-    from . import distributed as thd
-    group = _comm.get_group("ensemble")
-    n, me = dist.get_world_size(group), dist.get_rank(group)
-    N = forecasts.shape[-1]
-    sizes = thd.compute_split_shapes(N, n)
-    a = sum(sizes[:me])
-    b = a + sizes[me]
-    f = _EnsembleTransposeFn.apply(forecasts, group)
-    return f, obs[..., a:b].contiguous(), q[..., a:b].contiguous(), (wgt[..., a:b].contiguous() if wgt is not None else None), group
-
-
-class _ReduceFromGroupFn(torch.autograd.Function):
-    """``reduce_from_parallel_region``: SUM all-reduce forward, identity backward"""
-
-    @staticmethod
-    def forward(ctx, x, group):
-        from . import ops
-        y = x.clone()
-        ops._all_reduce_sum(y, group)
-        return y
-
-    @staticmethod
-    def backward(ctx, g):
-        return g, None
-
-
-def _ensemble_active(flag) -> bool:
-    """``ensemble_distributed`` is honoured when the process-group tree names a split "ensemble" group.  The tree may not have
-    been looked at yet (a loss constructed before any makani_amd network under makani's own driver): adopt makani's tree first;
-    a set flag without such a group in a multi-rank job is reported — each rank would otherwise silently score its local
-    members only."""
-    if not flag:
-        return False
-    from . import comm as _comm
-    _comm.autodetect()
-    active = _comm.is_distributed("ensemble") and _comm.get_size("ensemble") > 1
-    if not active and _comm.get_world_size() > 1:
-        import warnings
-        warnings.warn("ensemble_distributed=True, but the process-group tree has no split 'ensemble' group: the loss scores the "
-                      "members of this rank only (makani_amd.comm.init(h, w, ensemble=n) or makani's own tree provides the group)")
-    return active
-
-
 def _check_finite_weights(w):
     """Non-finite ``ensemble_weights`` are rejected at construction.  Deviation from the reference, stated: its kernels fold
     ``isnan(weights)`` into their NaN mask (``crps_loss.py:66-73,176-177``), so a NaN weight — one entry per member, broadcast
@@ -510,7 +417,58 @@ def _ens_w(w, E, crps_type="cdf"):
     return w if crps_type == "cdf" else None          # only the cdf kernel reads the values (PWM accepts and ignores them)
 
 
-class CRPSLoss(nn.Module):
+class _EnsembleLoss(nn.Module):
+    """What the ensemble losses on the grid share (``GeometricBaseLoss`` of ``base_loss.py:261-342`` as the reference's use
+    it): the quadrature of the (local) grid, the loss type, the channel count and weighting, the input checks, and the way
+    from (B, E, C, H, W) members to the operands of a kernel over N points."""
+
+    def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed):
+        super().__init__()
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
+        self.spatial_distributed = self.quadrature.distributed
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)                 # crps_loss.py:305-307
+        # (the whole plane's weights: the ensemble-parallel path takes this rank's share of the points in forward)
+        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
+    @property
+    def n_channels(self):
+        return len(self.channel_names)
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    @staticmethod
+    def _check(forecasts, observations, spatial_weights):
+        check_forecast_dims(forecasts)
+        check_weight_dims(spatial_weights, observations)
+
+    def _points(self, forecasts, observations, spatial_weights):
+        """forecasts (B, E, C, H, W), observations (B, C, H, W), weights broadcastable to them or None -> f (B, E, C, N),
+        o (B, C, N), q (N), w (B, C, N) | None and ``sum_groups``, the process groups over which what the kernel sums over its
+        N points has to be added: the ensemble group (members <-> a share of the points) before the spatial group."""
+        f, o, q, w, group = flatten_and_split(forecasts, observations, self.quad_weight_split.reshape(-1), spatial_weights,
+                                              self.ensemble_distributed)
+        groups = [] if group is None else [group]
+        if self.spatial_distributed:
+            from . import distributed as thd
+            groups.append(thd.spatial_group())
+        return f, o, q, w, groups
+
+    @staticmethod
+    def _sum_shares(score, sum_groups):
+        for group in sum_groups:
+            score = ReduceFromGroupFn.apply(score, group)
+        return score
+
+
+class CRPSLoss(_EnsembleLoss):
     """``CRPSLoss`` of ``makani/utils/losses/crps_loss.py:277-452``: ``forward(forecasts (B, E, C, H, W), observations
     (B, C, H, W), spatial_weights=None) -> (B, C)``, the quadrature-weighted ensemble CRPS.  Score and quadrature are one HIP
     kernel (``csrc/crps.hip``), the gradient with respect to the forecasts one more.  Built: ``crps_type`` "skillspread"
@@ -524,13 +482,7 @@ class CRPSLoss(nn.Module):
                  spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
                  ensemble_weights: Optional[torch.Tensor] = None, alpha: Optional[float] = 1.0, eps: Optional[float] = 1.0e-6,
                  **kwargs):
-        super().__init__()
-        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
-        self.channel_names = channel_names
-        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
-                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
-        self.spatial_distributed = self.quadrature.distributed
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)                # crps_loss.py:305-307
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
         # the reference hands ensemble_weights to the "cdf" kernel (:392-396) and to the "probability weighted moment" kernel
         # (:404-409), which ignores their values: accepted for both (and ignored by the latter, as there); other forms raise
         if ensemble_weights is not None and crps_type not in ("cdf", "probability weighted moment"):
@@ -543,39 +495,30 @@ class CRPSLoss(nn.Module):
         self.crps_type, self.alpha, self.eps = crps_type, alpha, eps
         self.register_buffer("ensemble_weights", None if ensemble_weights is None else ensemble_weights.float().reshape(-1).contiguous(),
                              persistent=False)
-        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
-
-    @property
-    def n_channels(self):
-        return len(self.channel_names)
 
     @torch.compiler.disable(recursive=True)
     @device_guard
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
                 **kwargs) -> torch.Tensor:
-        if forecasts.dim() != 5:
-            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
-        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
-            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
-                             f"observations (found {observations.dim()}).")
+        self._check(forecasts, observations, spatial_weights)
         B, E, Cc, H, W = forecasts.shape
         if E == 1 and not self.ensemble_distributed:            # |obs - forecast| under the quadrature (crps_loss.py:375-377)
             crps = self.quadrature.lp(forecasts.squeeze(1), observations, spatial_weights, 1.0).reshape(B, Cc)
             return crps
-        w = spatial_weights.expand(B, Cc, H, W) if spatial_weights is not None else None
-        q = self.quad_weight_split.reshape(-1)
-        if self.ensemble_distributed:
-            # members are spread over the ensemble group: trade them for a share of the grid points (crps_loss.py:362-373),
-            # score that share with all members, sum the shares (:441-442)
-            f, o, q, w, group = _ensemble_split(forecasts.reshape(B, E, Cc, H * W), observations.reshape(B, Cc, H * W), q,
-                                                w.reshape(B, Cc, H * W) if w is not None else None)
-            E = f.shape[1]
-            crps = CrpsFn.apply(f.unsqueeze(-1), o.unsqueeze(-1), q, w.unsqueeze(-1) if w is not None else None,
-                                _CRPS_TYPES[self.crps_type], self.alpha, self.eps, _ens_w(self.ensemble_weights, E, self.crps_type))
-            return self.quadrature._reduce(_ReduceFromGroupFn.apply(crps, group))
-        crps = CrpsFn.apply(forecasts, observations, q, w,
-                            _CRPS_TYPES[self.crps_type], self.alpha, self.eps, _ens_w(self.ensemble_weights, E, self.crps_type))
-        return self.quadrature._reduce(crps)
+        # members spread over the ensemble group are traded for a share of the grid points (crps_loss.py:362-373); that share
+        # is scored with all members and the shares are summed (:441-442)
+        f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
+        crps = CrpsFn.apply(f.unsqueeze(-1), o.unsqueeze(-1), q, w.unsqueeze(-1) if w is not None else None,
+                            _CRPS_TYPES[self.crps_type], self.alpha, self.eps, _ens_w(self.ensemble_weights, f.shape[1], self.crps_type))
+        return self._sum_shares(crps, groups)
+
+
+def _sht_pair(sht, forecasts, observations):
+    """the coefficients of members and observation as the spectral ensemble losses take them: fp32, autocast off, / sqrt(4 pi)"""
+    with torch.autocast(device_type=forecasts.device.type, enabled=False):
+        f = sht(forecasts.float()) / math.sqrt(4.0 * math.pi)
+        o = sht(observations.float()) / math.sqrt(4.0 * math.pi)
+    return f, o
 
 
 class SpectralCRPSLoss(SpectralLpLoss):
@@ -594,7 +537,7 @@ class SpectralCRPSLoss(SpectralLpLoss):
                  eps: Optional[float] = 1.0e-6, **kwargs):
         super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed=spatial_distributed,
                          lmax=lmax)
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)
         if ensemble_weights is not None and crps_type != "cdf":
             raise NotImplementedError("currently only constant ensemble weights are supported")
         _check_finite_weights(ensemble_weights)
@@ -613,14 +556,10 @@ class SpectralCRPSLoss(SpectralLpLoss):
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spectral_weights: Optional[torch.Tensor] = None,
                 **kwargs) -> torch.Tensor:
         from . import distributed as thd
-        if forecasts.dim() != 5:
-            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
-        if spectral_weights is not None and spectral_weights.dim() != observations.dim():
-            raise ValueError("the weights have to have the same number of dimensions as observations")
+        check_forecast_dims(forecasts)
+        check_weight_dims(spectral_weights, observations, found=False)
         dtype = forecasts.dtype
-        with torch.autocast(device_type=forecasts.device.type, enabled=False):
-            f = self.sht(forecasts.float()) / math.sqrt(4.0 * math.pi)
-            o = self.sht(observations.float()) / math.sqrt(4.0 * math.pi)
+        f, o = _sht_pair(self.sht, forecasts, observations)
         if self.absolute:
             f, o = torch.abs(f).to(dtype), torch.abs(o).to(dtype)
         B, E, Cc, L, M = f.shape
@@ -628,11 +567,11 @@ class SpectralCRPSLoss(SpectralLpLoss):
             if not self.absolute:
                 raise NotImplementedError("the ensemble-parallel spectral CRPS is built for absolute=True")
             w = (spectral_weights.expand(B, Cc, L, M).reshape(B, Cc, L * M) if spectral_weights is not None else None)
-            fe, oe, qe, we, group = _ensemble_split(f.reshape(B, E, Cc, L * M), o.reshape(B, Cc, L * M),
+            fe, oe, qe, we, group = ensemble_split(f.reshape(B, E, Cc, L * M), o.reshape(B, Cc, L * M),
                                                     self.lm_weights.reshape(-1).contiguous(), w)
             crps = CrpsFn.apply(fe.unsqueeze(-1), oe.unsqueeze(-1), qe, we.unsqueeze(-1) if we is not None else None,
                                 _CRPS_TYPES[self.crps_type], self.alpha, self.eps, _ens_w(self.ensemble_weights, fe.shape[1]))
-            crps = _ReduceFromGroupFn.apply(crps, group)
+            crps = ReduceFromGroupFn.apply(crps, group)
             return thd.reduce_from_spatial_region(crps) if self.spatial_distributed else crps
         if not self.absolute and E > 1:        # the naive kernel on the complex coefficients themselves (crps_loss.py:605-608)
             w = spectral_weights.expand(B, Cc, L, M) if spectral_weights is not None else None
@@ -688,12 +627,11 @@ def channel_weighting(channel_names, channel_weight_type, time_diff_scale=None):
     return w
 
 
-class _EnsembleGridLoss(nn.Module):
+class _EnsembleGridLoss(_EnsembleLoss):
     """what ``GradientCRPSLoss`` and ``VortDivCRPSLoss`` share: constructor checks, quadrature, the score on the grid"""
 
     def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
                  ensemble_distributed, ensemble_weights, alpha, eps):
-        super().__init__()
         if spatial_distributed or ensemble_distributed:
             from . import comm as _comm
             _comm.autodetect()
@@ -701,11 +639,7 @@ class _EnsembleGridLoss(nn.Module):
                     (ensemble_distributed and _comm.is_distributed("ensemble") and _comm.get_size("ensemble") > 1):
                 raise NotImplementedError(f"{type(self).__name__}: the distributed vector transforms are not built yet "
                                           "(spatial_distributed / ensemble_distributed with a group larger than one)")
-        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
-        self.channel_names = channel_names
-        self.spatial_distributed = self.ensemble_distributed = False
-        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
-                                         crop_offset=crop_offset, normalize=True, distributed=False)
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, False, False)          # serial only
         if tuple(crop_shape) != tuple(img_shape):
             raise NotImplementedError("the vector-transform losses score the whole sphere (crop_shape == img_shape)")
         if crps_type not in ("skillspread", "naive skillspread") and alpha < 1.0:
@@ -716,21 +650,11 @@ class _EnsembleGridLoss(nn.Module):
         self.crps_type, self.alpha, self.eps = crps_type, alpha, eps
         self.register_buffer("ensemble_weights", None if ensemble_weights is None else ensemble_weights.float().reshape(-1).contiguous(),
                              persistent=False)
-        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
-
-    @property
-    def type(self):
-        return "probabilistic"                                                  # LossType.Probabilistic
 
     @staticmethod
     def _check(forecasts, observations, spatial_weights):
-        if forecasts.dim() != 5:
-            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
-        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
-            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
-                             f"observations (found {observations.dim()}).")
-        if not forecasts.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        _EnsembleLoss._check(forecasts, observations, spatial_weights)
+        need_gpu(forecasts)
 
     def _score(self, forecasts, observations, spatial_weights):
         """forecasts (B, E, C, H, W), observations (B, C, H, W) -> (B, C), as ``CRPSLoss.forward``"""
@@ -823,10 +747,6 @@ class VortDivCRPSLoss(_EnsembleGridLoss):
         self.vsht = RealVectorSHT(*img_shape, lmax=lmax, mmax=lmax, grid=grid_type)
         self.isht = InverseRealVectorSHT(self.vsht.nlat, self.vsht.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
 
-    @property
-    def n_channels(self):
-        return len(self.channel_names)
-
     def average_wind_weights(self, chw):
         wind = self.wind_chans.to(chw.device)
         u, v = wind[0::2], wind[1::2]
@@ -873,18 +793,19 @@ class EnergyScoreFn(torch.autograd.Function):
     """The three stages of ``csrc/escore.hip``.  forecasts (B, E, C, N) f32 | bf16 | complex64 in that layout, obs (B, C, N),
     q (N), wgt optional (B, C, N); the plane of N points is ``nseg`` segments.  ``mk_escore_sums`` -> sums (B, C, nseg, K);
     the sums are added over ``sum_groups`` (process groups: the all-reduces of the parallel variants fall BEFORE the root);
-    ``mk_escore_finish`` -> loss (B, C_out) and the table d loss / d sums, kept for ``mk_escore_grad``.  Gradient with
-    respect to the forecasts only (the backward of a SUM all-reduce is the identity)."""
+    ``finish(sums, loss, table, B, E, C, nseg, reduce, p)`` — ``_escore_finish`` or ``_mmd_finish`` with their scalars —
+    -> loss (B, C_out) and the table d loss / d sums, kept for ``mk_escore_grad``.  Gradient with respect to the forecasts
+    only (the backward of a SUM all-reduce is the identity)."""
 
     @staticmethod
-    def forward(ctx, forecasts, obs, q, wgt, scale, nseg, nanmode, reduce, p, beta, alpha, eps, sum_groups):
+    def forward(ctx, forecasts, obs, q, wgt, nseg, nanmode, reduce, p, finish, sum_groups):
         B, E, Cc, N = forecasts.shape
         if forecasts.is_complex():
             kind = _ES_COMPLEX
             f = torch.view_as_real(forecasts.to(torch.complex64).contiguous())
             o = torch.view_as_real(obs.to(torch.complex64).contiguous())
         else:
-            f = _prep(forecasts)
+            f = prep(forecasts)
             kind = dtype_code(f)
             o = obs.float().contiguous()
         q = q.float().contiguous()
@@ -901,9 +822,7 @@ class EnergyScoreFn(torch.autograd.Function):
         Cout = 1 if reduce else Cc
         loss = torch.empty((B, Cout), dtype=torch.float32, device=f.device)
         table = torch.empty((B, Cout, nseg, K), dtype=torch.float32, device=f.device)
-        sc = scale.float().contiguous() if scale is not None else None
-        check(lib().mk_escore_finish(ptr(sums), ptr(sc), sc.numel() if sc is not None else 0, ptr(loss), ptr(table), B, E, Cc, nseg,
-                                     int(reduce), float(p), float(beta), float(alpha), float(eps), stream()), "mk_escore_finish")
+        finish(sums, loss, table, B, E, Cc, nseg, reduce, p)
         ctx.save_for_backward(f, o, q, w if w is not None else torch.empty(0, device=f.device), table)
         ctx.meta = (kind, w is not None, nseg, nanmode, float(p), forecasts.dtype)
         return loss
@@ -918,27 +837,26 @@ class EnergyScoreFn(torch.autograd.Function):
         check(lib().mk_escore_grad(ptr(f), kind, ptr(o), ptr(q), ptr(w) if has_w else None, ptr(table), ptr(go), ptr(gf), B, E, Cc,
                                    table.shape[1], N, nseg, nanmode, p, stream()), "mk_escore_grad")
         gf = torch.view_as_complex(gf) if kind == _ES_COMPLEX else gf.to(dt)
-        return (gf,) + (None,) * 12
+        return (gf,) + (None,) * 9
+
+
+def _escore_finish(scale, beta, alpha, eps):
+    """stage 2 of the energy scores (``mk_escore_finish``); ``scale`` (1 | C_out entries, or None) tempers the spread term"""
+    def finish(sums, loss, table, B, E, Cc, nseg, reduce, p):
+        sc = scale.float().contiguous() if scale is not None else None
+        check(lib().mk_escore_finish(ptr(sums), ptr(sc), sc.numel() if sc is not None else 0, ptr(loss), ptr(table), B, E, Cc, nseg,
+                                     int(reduce), float(p), float(beta), float(alpha), float(eps), stream()), "mk_escore_finish")
+    return finish
 
 
 def _escore_checks(forecasts, ensemble_weights):
-    if forecasts.dim() != 5:
-        raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
+    check_forecast_dims(forecasts)
     if ensemble_weights is not None:
         raise NotImplementedError("currently only constant ensemble weights are supported")
 
 
-def _escore_size_check(E):
-    if E > MAX_ENSEMBLE:
-        raise NotImplementedError(f"ensemble size {E}: the HIP energy-score kernels are built for 1 <= E <= {MAX_ENSEMBLE}")
-
-
 class _EnergyScoreMixin:
-    """what the three energy-score classes share with the reference's: the loss type, the channel count and weighting"""
-
-    @property
-    def type(self):
-        return "probabilistic"                                                  # LossType.Probabilistic
+    """what ``channel_reduction`` changes: one output channel, with weight one"""
 
     @property
     def n_channels(self):
@@ -950,7 +868,7 @@ class _EnergyScoreMixin:
         return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
 
 
-class LpEnergyScoreLoss(_EnergyScoreMixin, nn.Module):
+class LpEnergyScoreLoss(_EnergyScoreMixin, _EnsembleLoss):
     """``LpEnergyScoreLoss`` of ``makani/utils/losses/energy_score.py:30-250`` ("lp_energy_score"; "l2_energy_score" is the
     alias ``L2EnergyScoreLoss``): mean_e ||o - f_e||^beta - (E - 1 + alpha) / (E^2 (E - 1)) sum_{i<j} ||f_i - f_j||^beta with
     the quadrature-weighted Lebesgue norm ||x|| = (sum_n q w |x_n|^p)^(1/p) over the grid, per channel or (``channel_reduction``)
@@ -966,19 +884,12 @@ class LpEnergyScoreLoss(_EnergyScoreMixin, nn.Module):
                  ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
                  channel_reduction: Optional[bool] = True, alpha: Optional[float] = 1.0, beta: Optional[float] = 1.0,
                  p: Optional[float] = 2.0, eps: Optional[float] = 1.0e-6, spread_temper_steps: Optional[int] = 0, **kwargs):
-        super().__init__()
         if float(p) < 1.0:
             raise NotImplementedError(f"p = {p}: the energy score is built for p >= 1 (the gradient of |d|^p is unbounded at "
                                       "coincident members for p < 1)")
-        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
-        self.channel_names = channel_names
-        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
-                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
-        self.spatial_distributed = self.quadrature.distributed
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
         self.channel_reduction, self.alpha, self.beta, self.p, self.eps = channel_reduction, alpha, beta, float(p), eps
         self.spread_temper_steps = spread_temper_steps
-        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
         self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
 
     @torch.compiler.disable(recursive=True)
@@ -986,30 +897,18 @@ class LpEnergyScoreLoss(_EnergyScoreMixin, nn.Module):
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
                 lead_time_step: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         _escore_checks(forecasts, self.ensemble_weights)
-        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
-            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
-                             f"observations (found {observations.dim()}).")
-        if not forecasts.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
-        B, E, Cc, H, W = forecasts.shape
-        f = forecasts.reshape(B, E, Cc, H * W)
-        o = observations.reshape(B, Cc, H * W)
-        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
-        q = self.quad_weight_split.reshape(-1)
-        groups = []
-        if self.ensemble_distributed:               # members <-> a share of the points (:139-151), the sums added over the group (:188-190)
-            f, o, q, w, group = _ensemble_split(f, o, q, w)
-            groups.append(group)
-        if self.spatial_distributed:
-            from . import distributed as thd
-            groups.append(thd.spatial_group())
-        _escore_size_check(f.shape[1])
+        check_weight_dims(spatial_weights, observations)
+        need_gpu(forecasts)
+        # members <-> a share of the points (:139-151), the sums added over the group (:188-190)
+        f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
+        ensemble_size_check(f.shape[1], "energy-score")
         scale = None
         if self.training and self.spread_temper_steps > 0 and lead_time_step is not None:       # :243-245
             scale = torch.clamp(lead_time_step.float().to(f.device) / self.spread_temper_steps, min=1.0).reshape(-1)
             if scale.numel() not in (1, self.n_channels):
                 raise ValueError(f"lead_time_step holds {scale.numel()} entries for {self.n_channels} output channels")
-        return EnergyScoreFn.apply(f, o, q, w, scale, 1, 0, self.channel_reduction, self.p, self.beta, self.alpha, self.eps, groups)
+        return EnergyScoreFn.apply(f, o, q, w, 1, 0, self.channel_reduction, self.p,
+                                   _escore_finish(scale, self.beta, self.alpha, self.eps), groups)
 
 
 L2EnergyScoreLoss = LpEnergyScoreLoss          # backward-compatibility alias, as the reference's
@@ -1024,18 +923,11 @@ class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
                  ensemble_distributed, ensemble_weights, channel_reduction, alpha, beta, eps):
         SpectralLpLoss.__init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type,
                                 spatial_distributed=spatial_distributed, lmax=lmax, eps=eps)
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)
         self.channel_reduction, self.alpha, self.beta = channel_reduction, alpha, beta
         self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
 
-    def _coefficients(self, forecasts, observations):
-        _escore_checks(forecasts, self.ensemble_weights)
-        if not forecasts.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
-        with torch.autocast(device_type=forecasts.device.type, enabled=False):
-            f = self.sht(forecasts.float()) / math.sqrt(4.0 * math.pi)
-            o = self.sht(observations.float()) / math.sqrt(4.0 * math.pi)
-        return f, o
+    type = _EnsembleLoss.type                                                   # (the rest of that base belongs to the grid)
 
     def _ensemble_split_lm(self, f, o, q):
         """f (B, E_loc, C, L, M) complex, o (B, C, L, M), q (L, M): the members of the group on this rank's share of the
@@ -1043,14 +935,16 @@ class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
         (re, im) travel as two rows of the channel axis."""
         B, E, Cc, L, M = f.shape
         fr = torch.view_as_real(f.contiguous()).permute(0, 1, 2, 3, 5, 4).reshape(B, E, Cc * L * 2, M)
-        fr, os_, qs, _, group = _ensemble_split(fr, o, q, None)
+        fr, os_, qs, _, group = ensemble_split(fr, o, q, None)
         Ml = fr.shape[-1]
         fs = torch.view_as_complex(fr.reshape(B, -1, Cc, L, 2, Ml).permute(0, 1, 2, 3, 5, 4).contiguous())
         return fs, os_, qs, group
 
     def _score(self, forecasts, observations, per_degree):
         from . import comm as _comm
-        f, o = self._coefficients(forecasts, observations)
+        _escore_checks(forecasts, self.ensemble_weights)
+        need_gpu(forecasts)
+        f, o = _sht_pair(self.sht, forecasts, observations)
         q = self.lm_weights
         groups = []
         if self.ensemble_distributed:
@@ -1063,11 +957,11 @@ class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
             elif _comm.get_size("w") > 1:
                 groups.append(_comm.get_group("w"))
         B, E, Cc, L, M = f.shape
-        _escore_size_check(E)
-        loss = EnergyScoreFn.apply(f.reshape(B, E, Cc, L * M), o.reshape(B, Cc, L * M), q.reshape(-1), None, None,
-                                   L if per_degree else 1, 1, self.channel_reduction, 2.0, self.beta, self.alpha, self.eps, groups)
+        ensemble_size_check(E, "energy-score")
+        loss = EnergyScoreFn.apply(f.reshape(B, E, Cc, L * M), o.reshape(B, Cc, L * M), q.reshape(-1), None, L if per_degree else 1, 1,
+                                   self.channel_reduction, 2.0, _escore_finish(None, self.beta, self.alpha, self.eps), groups)
         if per_degree and self.spatial_distributed and _comm.get_size("h") > 1:
-            loss = _ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+            loss = ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
         return loss
 
 
@@ -1178,8 +1072,7 @@ class SpectralAMSELoss(SpectralLpLoss):
     def forward(self, prd: torch.Tensor, tar: torch.Tensor, wgt: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
         if prd.dim() != 4:
             raise ValueError(f"expected (B, C, H, W), got {tuple(prd.shape)}")
-        if not prd.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
+        need_gpu(prd)
         from . import comm as _comm
         ptype = prd.dtype
         with torch.autocast(device_type=prd.device.type, enabled=False):
@@ -1189,14 +1082,14 @@ class SpectralAMSELoss(SpectralLpLoss):
         w = wgt.to(x.device).expand(B, Cc, L, M) if wgt is not None else None
         sums = AmseSumsFn.apply(x, y, w, self._l_off - self._m_off, self._m_off)
         if self.spatial_distributed and _comm.get_size("w") > 1:
-            sums = _ReduceFromGroupFn.apply(sums, _comm.get_group("w"))
+            sums = ReduceFromGroupFn.apply(sums, _comm.get_group("w"))
         xnorm2, ynorm2, xycoh_sum = sums.unbind(-1)
         xnorm, ynorm = torch.sqrt(xnorm2), torch.sqrt(ynorm2)
         xycoh = xycoh_sum / torch.sqrt(xnorm2 * ynorm2 + self.eps)             # eps inside the root (:104)
         loss = torch.square(xnorm - ynorm) + 2 * torch.maximum(xnorm2, ynorm2) * (1 - xycoh)
         loss = torch.sum(loss, dim=-1)
         if self.spatial_distributed and _comm.get_size("h") > 1:
-            loss = _ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+            loss = ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
         return loss.to(ptype)
 
 
@@ -1207,7 +1100,7 @@ class EnsNllFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, forecasts, obs, q, wgt, eps):
         B, E, Cc, N = forecasts.shape
-        f = _prep(forecasts)
+        f = prep(forecasts)
         o = obs.float().contiguous()
         q = q.float().contiguous()
         w = wgt.float().contiguous() if wgt is not None else None
@@ -1231,12 +1124,7 @@ class EnsNllFn(torch.autograd.Function):
         return gf.to(dt), None, None, None, None
 
 
-def _ensemble_size_check(E, what):
-    if E > MAX_ENSEMBLE:
-        raise NotImplementedError(f"ensemble size {E}: the HIP {what} kernels are built for 1 <= E <= {MAX_ENSEMBLE}")
-
-
-class EnsembleNLLLoss(nn.Module):
+class EnsembleNLLLoss(_EnsembleLoss):
     """``EnsembleNLLLoss`` of ``makani/utils/losses/likelihood_loss.py:30-134`` ("ensemble_nll"): the negative log likelihood of
     the observation under a Gaussian with the ensemble's mean and (``correction=0``) variance, the variance clamped at
     ``eps^2``, under the quadrature.  ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W), spatial_weights=None)
@@ -1246,87 +1134,34 @@ class EnsembleNLLLoss(nn.Module):
     def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
                  channel_names: List[str], grid_type: str, spatial_distributed: Optional[bool] = False,
                  ensemble_distributed: Optional[bool] = False, eps: Optional[float] = 1.0e-6, **kwargs):
-        super().__init__()
-        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
-        self.channel_names = channel_names
-        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
-                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
-        self.spatial_distributed = self.quadrature.distributed
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
         self.eps = eps
-        # (the whole plane's weights: the ensemble-parallel path takes this rank's share of the points in forward, as CRPSLoss does)
-        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
-
-    @property
-    def type(self):
-        return "probabilistic"                                                  # LossType.Probabilistic
-
-    @property
-    def n_channels(self):
-        return len(self.channel_names)
-
-    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
-        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
 
     @torch.compiler.disable(recursive=True)
     @device_guard
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
                 **kwargs) -> torch.Tensor:
         B, E, Cc, H, W = forecasts.shape               # (a forecast without an ensemble axis fails here, as in the reference)
-        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
-            raise ValueError("the weights have to have the same number of dimensions as observations")
-        if not self.ensemble_distributed:
-            _ensemble_size_check(E, "likelihood")
-        if not forecasts.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
-        f = forecasts.reshape(B, E, Cc, H * W)
-        o = observations.reshape(B, Cc, H * W)
-        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
-        q = self.quad_weight_split.reshape(-1)
-        if self.ensemble_distributed:               # members <-> a share of the points (:108-118), the shares summed (:127-128)
-            f, o, q, w, group = _ensemble_split(f, o, q, w)
-            _ensemble_size_check(f.shape[1], "likelihood")
-            return self.quadrature._reduce(_ReduceFromGroupFn.apply(EnsNllFn.apply(f, o, q, w, self.eps), group))
-        return self.quadrature._reduce(EnsNllFn.apply(f, o, q, w, self.eps))
+        check_weight_dims(spatial_weights, observations, found=False)
+        if not self.ensemble_distributed:           # (the members of the whole group are counted after the exchange)
+            ensemble_size_check(E, "likelihood")
+        need_gpu(forecasts)
+        # members <-> a share of the points (:108-118), the shares summed (:127-128)
+        f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
+        ensemble_size_check(f.shape[1], "likelihood")
+        return self._sum_shares(EnsNllFn.apply(f, o, q, w, self.eps), groups)
 
 
-class MmdFn(EnergyScoreFn):
-    """``GaussianMMDLoss`` on the energy-score pipeline: stage 1 (``mk_escore_sums``, p = beta, one segment, a NaN observation
-    or member masks the point), the sums added over ``sum_groups``, ``mk_mmd_finish`` -> loss (B, C_out) and the table
-    d loss / d sums; the backward is stage 3 (``mk_escore_grad``) as inherited."""
-
-    @staticmethod
-    def forward(ctx, forecasts, obs, q, wgt, reduce, beta, sigma, alpha, sum_groups):
-        B, E, Cc, N = forecasts.shape
-        f = _prep(forecasts)
-        kind = dtype_code(f)
-        o = obs.float().contiguous()
-        q = q.float().contiguous()
-        w = wgt.float().contiguous() if wgt is not None else None
-        K = E + E * (E - 1) // 2
-        sums = torch.empty((B, Cc, 1, K), dtype=torch.float32, device=f.device)
-        nws = lib().mk_escore_sums_workspace(B, E, Cc, N, 1, 1)
-        ws = torch.empty((nws,), dtype=torch.float32, device=f.device) if nws else None
-        check(lib().mk_escore_sums(ptr(f), kind, ptr(o), ptr(q), ptr(w), ptr(sums), ptr(ws), B, E, Cc, N, 1, 1, float(beta), stream()),
-              "mk_escore_sums")
-        from . import ops
-        for group in sum_groups:
-            ops._all_reduce_sum(sums, group)
-        Cout = 1 if reduce else Cc
-        loss = torch.empty((B, Cout), dtype=torch.float32, device=f.device)
-        table = torch.empty((B, Cout, 1, K), dtype=torch.float32, device=f.device)
+def _mmd_finish(sigma, alpha):
+    """stage 2 of ``GaussianMMDLoss`` (``mk_mmd_finish``) between stages 1 and 3 of the energy-score pipeline: p = beta, one
+    segment, a NaN observation or member masks the point"""
+    def finish(sums, loss, table, B, E, Cc, nseg, reduce, p):
         check(lib().mk_mmd_finish(ptr(sums), ptr(loss), ptr(table), B, E, Cc, int(reduce), float(sigma), float(alpha), stream()),
               "mk_mmd_finish")
-        ctx.save_for_backward(f, o, q, w if w is not None else torch.empty(0, device=f.device), table)
-        ctx.meta = (kind, w is not None, 1, 1, float(beta), forecasts.dtype)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        return EnergyScoreFn.backward(ctx, g)[:1] + (None,) * 8
+    return finish
 
 
-class GaussianMMDLoss(nn.Module):
+class GaussianMMDLoss(_EnergyScoreMixin, _EnsembleLoss):
     """``GaussianMMDLoss`` of ``makani/utils/losses/mmd_loss.py:30-219`` ("gaussian_mmd", arXiv:1505.03906): with the distances
     s(a, b) = sum_n q w |a_n - b_n|^beta (per channel, or summed over the channels with ``channel_reduction``) and the kernel
     k = exp(-s^2 / 2 sigma):  mean_e k(o, f_e) - (E - 1 + alpha) / (2 E^2 (E - 1)) sum_{i != j} k(f_i, f_j).
@@ -1344,27 +1179,12 @@ class GaussianMMDLoss(nn.Module):
                  ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
                  sigma: Optional[float] = 1.0, alpha: Optional[float] = 1.0, beta: Optional[float] = 2.0,
                  channel_reduction: Optional[bool] = False, **kwargs):
-        super().__init__()
         if float(beta) < 1.0:
             raise NotImplementedError(f"beta = {beta}: the Gaussian MMD is built for beta >= 1 (the gradient of |d|^beta is unbounded "
                                       "at coincident members for beta < 1)")
-        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
-        self.channel_names = channel_names
-        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
-                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
-        self.spatial_distributed = self.quadrature.distributed
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
         self.alpha, self.beta, self.channel_reduction, self.sigma = alpha, beta, channel_reduction, sigma
-        self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1).contiguous(), persistent=False)
         self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
-
-    @property
-    def type(self):
-        return "probabilistic"                                                  # LossType.Probabilistic
-
-    @property
-    def n_channels(self):
-        return 1 if self.channel_reduction else len(self.channel_names)
 
     def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: str = None) -> torch.Tensor:
         return torch.ones(1)
@@ -1373,28 +1193,13 @@ class GaussianMMDLoss(nn.Module):
     @device_guard
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
                 **kwargs) -> torch.Tensor:
-        if forecasts.dim() != 5:
-            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
-        if spatial_weights is not None and spatial_weights.dim() != observations.dim():
-            raise ValueError(f"the weights have to have the same number of dimensions (found {spatial_weights.dim()}) as "
-                             f"observations (found {observations.dim()}).")
+        self._check(forecasts, observations, spatial_weights)
         if self.ensemble_weights is not None:
             raise NotImplementedError("currently only constant ensemble weights are supported")
-        B, E, Cc, H, W = forecasts.shape
-        if not self.ensemble_distributed:
-            _ensemble_size_check(E, "MMD")
-        if not forecasts.is_cuda:
-            raise RuntimeError("makani_amd losses run on the GPU (HIP) path only")
-        f = forecasts.reshape(B, E, Cc, H * W)
-        o = observations.reshape(B, Cc, H * W)
-        w = spatial_weights.expand(B, Cc, H, W).reshape(B, Cc, H * W) if spatial_weights is not None else None
-        q = self.quad_weight_split.reshape(-1)
-        groups = []
-        if self.ensemble_distributed:               # members <-> a share of the points (:131-145), the sums added over the group (:180-182)
-            f, o, q, w, group = _ensemble_split(f, o, q, w)
-            groups.append(group)
-            _ensemble_size_check(f.shape[1], "MMD")
-        if self.spatial_distributed:
-            from . import distributed as thd
-            groups.append(thd.spatial_group())
-        return MmdFn.apply(f, o, q, w, self.channel_reduction, self.beta, self.sigma, self.alpha, groups)
+        if not self.ensemble_distributed:           # (the members of the whole group are counted after the exchange)
+            ensemble_size_check(forecasts.shape[1], "MMD")
+        need_gpu(forecasts)
+        # members <-> a share of the points (:131-145), the sums added over the group (:180-182)
+        f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
+        ensemble_size_check(f.shape[1], "MMD")
+        return EnergyScoreFn.apply(f, o, q, w, 1, 1, self.channel_reduction, self.beta, _mmd_finish(self.sigma, self.alpha), groups)

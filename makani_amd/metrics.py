@@ -13,7 +13,7 @@ ensemble of one member yields what the reference's arithmetic yields (NaN for sp
 
 ``spatial_distributed`` adds the sums over the spatial group before the finish.  ``ensemble_distributed`` (SSR, rank histogram;
 Spread whenever the "ensemble" group has more than one rank, as the reference) trades this rank's members for all members on a
-share of the points (``losses._ensemble_split``) and adds the sums over the ensemble group: no field-sized all-reduce of the
+share of the points (``ensemble.ensemble_split``) and adds the sums over the ensemble group: no field-sized all-reduce of the
 mean.  ACC's ``bias`` is cut to the local lat/lon shard at construction (functions.py:165-169).
 
 Deviations from the reference, stated:
@@ -31,9 +31,9 @@ import torch
 import torch.nn as nn
 
 from . import comm as _comm
-from ._lib import check, device_guard, dtype_code, lib, ptr, stream
-from .losses import (CRPSLoss, GridQuadrature, _ensemble_active, _ensemble_size_check, _ensemble_split, _prep,
-                     grid_to_quadrature_rule)
+from ._lib import check, device_guard, dtype_code, lib, need_gpu, prep, ptr, stream
+from .ensemble import check_forecast_dims, check_weight_dims, ensemble_active, ensemble_size_check, flatten_and_split
+from .losses import CRPSLoss, GridQuadrature, grid_to_quadrature_rule
 
 SUM_L1, SUM_L2, SUM_XY, SUM_XX, SUM_YY = 1, 2, 4, 8, 16          # MK_METRIC_* of include/makani_amd.h: bit k selects [..., k]
 SUM_ALL = 31
@@ -71,11 +71,6 @@ def _welford_reduction_helper(vals, counts, batch_reduction, dim):
     else:
         vals_res, counts_res = vals, counts
     return vals_res, counts_res
-
-
-def _need_gpu(t):
-    if not t.is_cuda:
-        raise RuntimeError("makani_amd metrics run on the GPU (HIP) path only")
 
 
 def _reduce(v, channel_reduction, batch_reduction):
@@ -129,14 +124,14 @@ def deterministic_sums(x: torch.Tensor, y: torch.Tensor, quadrature: GridQuadrat
     SUM_XY | SUM_XX | SUM_YY``) names the sums to form, the others stay 0.  ``quadrature`` supplies the weights of the (local)
     grid and, when it is distributed, the sum over the spatial group."""
     B, C, H, W = x.shape
-    xs = _prep(x).reshape(B, C, H * W)
-    ys = _prep(y, x.shape).reshape(B, C, H * W)
+    xs = prep(x).reshape(B, C, H * W)
+    ys = prep(y, x.shape).reshape(B, C, H * W)
     w = weight.float().expand(B, C, H, W).contiguous().reshape(B, C, H * W) if weight is not None else None
     b = _bias_plane(bias, C, H, W) if (bias is not None and (which & SUM_ACC)) else None
     q = quadrature.quad_weight.reshape(-1)
     if q.numel() != H * W:
         raise ValueError(f"the quadrature holds {q.numel()} weights for planes of {H} x {W} points")
-    _need_gpu(x)
+    need_gpu(x, "metrics")
     return quadrature._reduce(_det_launch(xs, ys, q, b, w, which))
 
 
@@ -170,26 +165,24 @@ class GeometricBaseMetric(nn.Module):
         return vals if self.batch_reduction == "mean" else vals / counts
 
     @torch.no_grad()
-    def _ensemble_sums(self, forecasts, observations, weight, which, ensemble_distributed, check_weight_dims=False):
+    def _ensemble_sums(self, forecasts, observations, weight, which, ensemble_distributed, check_weights=False):
         """(sums (B, C, E_tot + 3) over the whole sphere and the whole ensemble, E_tot)"""
-        if forecasts.dim() != 5:
-            raise ValueError(f"Error, forecasts tensor expected to have 5 dimensions but found {forecasts.dim()}.")
-        if check_weight_dims and (weight is not None) and (weight.dim() != observations.dim()):
-            raise ValueError(f"the weights have to have the same number of dimensions (found {weight.dim()}) as observations "
-                             f"(found {observations.dim()}).")
+        check_forecast_dims(forecasts)
+        if check_weights:
+            check_weight_dims(weight, observations)
         B, E, C, H, W = forecasts.shape
         if not ensemble_distributed:
-            _ensemble_size_check(E, "metric")
+            ensemble_size_check(E, "metric")
         if self.quadrature.quad_weight.numel() != H * W:
             raise ValueError(f"the quadrature holds {self.quadrature.quad_weight.numel()} weights for planes of {H} x {W} points")
-        _need_gpu(forecasts)
-        f = _prep(forecasts).reshape(B, E, C, H * W)
-        o = observations.float().expand(B, C, H, W).contiguous().reshape(B, C, H * W)
-        w = weight.float().expand(B, C, H, W).contiguous().reshape(B, C, H * W) if weight is not None else None
-        q = self.quadrature.quad_weight.reshape(-1)
-        if ensemble_distributed:          # members <-> a share of the points; the shares are summed below
-            f, o, q, w, group = _ensemble_split(f, o, q, w)
-        _ensemble_size_check(f.shape[1], "metric")
+        need_gpu(forecasts, "metrics")
+        # (the kernel takes its operands as they are: dense fp32 observations and weights of the full shape)
+        f = prep(forecasts)
+        o = observations.float().expand(B, C, H, W).contiguous()
+        w = weight.float().expand(B, C, H, W).contiguous() if weight is not None else None
+        # members <-> a share of the points; the shares are summed below
+        f, o, q, w, group = flatten_and_split(f, o, self.quadrature.quad_weight.reshape(-1), w, ensemble_distributed)
+        ensemble_size_check(f.shape[1], "metric")
         sums = _ens_launch(f, o, q, w, which)
         if ensemble_distributed:
             from . import ops
@@ -336,7 +329,7 @@ class GeometricSSR(GeometricBaseMetric):
                  spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False, **kwargs):
         super().__init__(grid_type=grid_type, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset, normalize=normalize,
                          channel_reduction=channel_reduction, batch_reduction=batch_reduction, spatial_distributed=spatial_distributed)
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)
         self.eps = eps
 
     @property
@@ -397,7 +390,7 @@ class GeometricRankHistogram(GeometricBaseMetric):
                  spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False, **kwargs):
         super().__init__(grid_type=grid_type, img_shape=img_shape, crop_shape=crop_shape, crop_offset=crop_offset, normalize=normalize,
                          channel_reduction=channel_reduction, batch_reduction=batch_reduction, spatial_distributed=spatial_distributed)
-        self.ensemble_distributed = _ensemble_active(ensemble_distributed)
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)
         # (the whole plane's weights: the ensemble-parallel path takes this rank's share of the points in forward, as CRPSLoss does)
         self.register_buffer("quad_weight_split", self.quadrature.quad_weight.reshape(1, 1, -1, 1).contiguous(), persistent=False)
 
@@ -411,5 +404,5 @@ class GeometricRankHistogram(GeometricBaseMetric):
     @torch.compiler.disable(recursive=True)
     @device_guard
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, weight: Optional[torch.Tensor] = None) -> torch.Tensor:
-        sums, _ = self._ensemble_sums(forecasts, observations, weight, ENS_HIST, self.ensemble_distributed, check_weight_dims=True)
+        sums, _ = self._ensemble_sums(forecasts, observations, weight, ENS_HIST, self.ensemble_distributed, check_weights=True)
         return _reduce(sums[..., 2:], self.channel_reduction, self.batch_reduction)

@@ -16,6 +16,8 @@ def test_crps_constructor_contract():
     m = ma.CRPSLoss(**kw)
     assert m.crps_type == "skillspread" and m.n_channels == 2 and m.quad_weight_split.shape == (1, 1, 144)
     assert abs(float(m.quad_weight_split.sum()) - 1.0) < 1e-6
+    assert m.type == "probabilistic"                                 # GeometricBaseLoss members (base_loss.py:333)
+    assert torch.equal(m.compute_channel_weighting("auto"), torch.full((2,), 0.01))
     with pytest.raises(ValueError):
         ma.CRPSLoss(crps_type="nonsense", **kw)
     assert ma.CRPSLoss(crps_type="cdf", **kw).crps_type == "cdf"
