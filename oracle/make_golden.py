@@ -26,7 +26,11 @@ import sys
 import numpy as np
 import torch
 
-from . import ref_shims
+if __package__:
+    from . import ref_shims
+else:                                   # run as a script: python oracle/make_golden.py
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from oracle import ref_shims
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 
@@ -409,9 +413,37 @@ def contraction_fixtures():
     wd = torch.randn(1, 6, 5, 9, 10, dtype=torch.complex64)
     y = con._contract_dense_pytorch(x, w, separable=False, operator_type="dhconv")
     yd = con._contract_dense_pytorch(x, wd, separable=False, operator_type="diagonal")
-    path = os.path.join(OUT, "contractions.npz")
-    np.savez_compressed(path, x=_np(x), w=_np(w), wd=_np(wd), y=_np(y), yd=_np(yd))
-    print(f"contractions.npz: {os.path.getsize(path)/1e6:.2f} MB")
+    _save_unless_same("contractions.npz", dict(x=_np(x), w=_np(w), wd=_np(wd), y=_np(y), yd=_np(yd)), frozen=True)
+
+    # the remaining contractions of contractions.py:17-54 (a generator of their own: the draws above stay what they were)
+    torch.manual_seed(8)
+    xs = torch.randn(2, 1, 6, 9, 10, dtype=torch.complex64)
+    ws_lm = torch.randn(1, 6, 9, 10, dtype=torch.complex64)
+    ws_l = torch.randn(1, 6, 9, dtype=torch.complex64)
+    xg = torch.randn(2, 2, 3, 9, 10, dtype=torch.complex64)
+    wg = torch.randn(2, 3, 2, 9, 10, dtype=torch.complex64)
+    rec = dict(xs=_np(xs), ws_lm=_np(ws_lm), ws_l=_np(ws_l), xg=_np(xg), wg=_np(wg),
+               ys_lm=_np(con._contract_dense_pytorch(xs, ws_lm, separable=True, operator_type="diagonal")),
+               ys_l=_np(con._contract_dense_pytorch(xs, ws_l, separable=True, operator_type="dhconv")),
+               yg=_np(con._contract_dense_pytorch(xg, wg, separable=False, operator_type="diagonal")))
+    _save_unless_same("contractions_sep.npz", rec)
+
+
+def _save_unless_same(name, rec, frozen=False):
+    """write tests/golden/<name> unless the file there already holds exactly these arrays (an .npz carries the time of
+    writing, so rewriting equal data would still change the file); a frozen file is never replaced"""
+    path = os.path.join(OUT, name)
+    if os.path.exists(path):
+        with np.load(path, allow_pickle=False) as old:
+            if sorted(old.files) == sorted(rec) and all(
+                    old[k].dtype == rec[k].dtype and old[k].shape == rec[k].shape and old[k].tobytes() == rec[k].tobytes() for k in rec):
+                print(f"{name}: unchanged")
+                return
+        if frozen:
+            print(f"{name}: regeneration gives DIFFERENT arrays; the committed file is kept (remove it by hand to replace it)")
+            return
+    np.savez_compressed(path, **rec)
+    print(f"{name}: {os.path.getsize(path)/1e6:.2f} MB")
 
 
 def loss_fixtures():

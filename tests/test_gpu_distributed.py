@@ -32,7 +32,7 @@ def _rel(a, b):
 TOL_Y, TOL_G = 5e-6, 2e-5
 
 
-def _worker(rank, world, port, h, w, norm="instance_norm"):
+def _worker(rank, world, port, h, w, norm="instance_norm", operator_type="dhconv", separable=False, max_modes=None):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
@@ -45,7 +45,9 @@ def _worker(rank, world, port, h, w, norm="instance_norm"):
         import makani_amd.distributed as thd
         dev = torch.device("cuda:0")
         cfg = dict(inp_shape=(37, 72), out_shape=(37, 72), inp_chans=4, out_chans=4, scale_factor=3, embed_dim=16,
-                   num_layers=3, mlp_ratio=2, normalization_layer=norm)
+                   num_layers=3, mlp_ratio=2, normalization_layer=norm, operator_type=operator_type, separable=separable)
+        if max_modes is not None:
+            cfg["max_modes"] = max_modes
         B = 2
         torch.manual_seed(11)
         serial = ma.SphericalFourierNeuralOperatorNet(**cfg).to(dev)
@@ -72,12 +74,19 @@ def _worker(rank, world, port, h, w, norm="instance_norm"):
         lat0, lon0 = sum(td.lat_shapes[:ih]), sum(td.lon_shapes[:iw])
         hl, wl = td.lat_shapes[ih], td.lon_shapes[iw]
         l0, ll = sum(td.l_shapes[:ih]), td.l_shapes[ih]
+        m0, ml = sum(td.m_shapes[:iw]), td.m_shapes[iw]
+        # the "diagonal" weight (dense or separable) has an m axis and is sharded over h and w; the "dhconv" weight (dense or
+        # separable) is sharded over h and shared over w (spectral_convolution.py:169-173,195-198)
+        if operator_type == "diagonal":
+            cut = lambda t: t[..., l0:l0 + ll, m0:m0 + ml]
+        else:
+            cut = lambda t: t[..., l0:l0 + ll]
         sd = serial.state_dict()
         own = model.state_dict()
         for k in own:
             src = sd[k]
             if k.endswith("filter.filter.weight"):
-                src = src[..., l0:l0 + ll]
+                src = cut(src)
             assert own[k].shape == src.shape, (k, own[k].shape, src.shape)
             own[k].copy_(src)
         xl = x[..., lat0:lat0 + hl, lon0:lon0 + wl].clone().requires_grad_(True)
@@ -91,10 +100,10 @@ def _worker(rank, world, port, h, w, norm="instance_norm"):
         worst = ("", 0.0)
         for k, p in model.named_parameters():
             g = (torch.view_as_real(p.grad) if p.grad.is_complex() else p.grad).detach().cpu().contiguous()
-            if k.endswith("filter.filter.weight"):           # sharded over h, shared over w
-                if wg is not None and w > 1:
+            if k.endswith("filter.filter.weight"):           # sharded over h, and shared over w ("dhconv") or sharded over w too
+                if operator_type == "dhconv" and wg is not None and w > 1:
                     dist.all_reduce(g, group=wg)
-                ref = torch.view_as_real(sref[k].grad[..., l0:l0 + ll].contiguous()).cpu()
+                ref = torch.view_as_real(cut(sref[k].grad).contiguous()).cpu()
             else:                                            # replicated: partial gradients sum over spatial
                 dist.all_reduce(g)
                 ref = sref[k].grad.cpu()
@@ -103,7 +112,7 @@ def _worker(rank, world, port, h, w, norm="instance_norm"):
             e = _rel(g, ref)
             worst = max(worst, (k, e), key=lambda t: t[1])
             assert e < TOL_G, (rank, k, e)
-        print(f"h{h}w{w} {norm} rank {rank}: y {e_y:.1e} gx {e_gx:.1e} worst parameter gradient {worst[0]} {worst[1]:.1e}", flush=True)
+        print(f"h{h}w{w} {norm} {operator_type}{' separable' if separable else ''} rank {rank}: y {e_y:.1e} gx {e_gx:.1e} worst parameter gradient {worst[0]} {worst[1]:.1e}", flush=True)
         dist.barrier()
     finally:
         dist.destroy_process_group()
@@ -122,6 +131,18 @@ def test_spatial_parallel_sfno_with_geometric_instance_norm_matches_serial(h, w)
     GeometricInstanceNormS2 network, forward, input gradient and every parameter gradient"""
     world = h * w
     mp.spawn(_worker, args=(world, _free_port(), h, w, "instance_norm_s2"), nprocs=world, join=True)
+
+
+@pytest.mark.parametrize("operator_type,separable", [("diagonal", False), ("diagonal", True), ("dhconv", True)],
+                         ids=["diagonal", "diagonal-separable", "dhconv-separable"])
+def test_spatial_parallel_sfno_other_operators_matches_serial(operator_type, separable):
+    """the contractions of csrc/spectral_pointwise.hip under h2 x w2 parallelism.  max_modes = (12, 12) instead of the toy
+    network's own 12 x 13: the reference's "diagonal" initialisation broadcasts its per-l scale against the m axis, so the
+    serial network and every rank need as many orders as degrees, here 12 and 6 / 6 (lmax = mmax = 12 split 6 / 6: two of the four
+    ranks have a first degree that differs from their first order, tri_off = +6, 0, -6): the "diagonal" weight, dense and
+    separable, is sharded over h AND w, so each rank's gradient is its window of the serial one with no reduction; the
+    separable "dhconv" weight is shared over w like the dense one"""
+    mp.spawn(_worker, args=(4, _free_port(), 2, 2, "instance_norm", operator_type, separable, (12, 12)), nprocs=4, join=True)
 
 
 class _OneRankTree:
