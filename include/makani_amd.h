@@ -121,10 +121,24 @@ int mk_sgemm_presplit_batched(const MkGemm* g, const void* a_planes, long long p
  *   mode 3 synthesis with t = 0: in is S (L, orders, 2, Rp) (the gradient of a scalar field).
  *   Modes 1 / 0 with the transposed matrices are the transposed maps of modes 0 / 1, modes 3 / 2 those of 2 / 3.
  *   band_lo / band_hi (device int[orders], optional): the latitude band outside of which BOTH matrices vanish; analysis
- *   clips the latitude sum, synthesis writes exact zeros outside.  Rows l < m + tri_off are skipped in 32-row steps. */
+ *   clips the latitude sum, synthesis writes exact zeros outside.  Rows l < m + tri_off are skipped in 32-row steps.
+ *   The m-shard form (an azimuth rank of the h x w distributed pair): `orders` consecutive orders starting at tri_off, i.e.
+ *   batch b is the GLOBAL order b + tri_off; planes, in / out and the band arrays are indexed by the LOCAL order b (the
+ *   caller hands over the slices [tri_off, tri_off + orders) of all of them).  Orders are independent batches, so the shard
+ *   launch writes the same bits, and leaves the same rows l < m unwritten, as the same orders of the full launch. */
 int mk_vlegendre(const void* planes0, const void* planes1, long long pl_stride, long long pl_batch, long long pl_k,
                  int limbs, const float* in, float* out, int mode, int rows, int K, int orders, int Rp, int tri_off,
                  const int* band_lo, const int* band_hi, void* stream);
+/* mk_vcols_repack (csrc/vcols.hip): pack / unpack side of the exchanges that split or join the PAIRS of a vector F / S tensor,
+ *   whose last axis is `blocks` (4, or 2 for the s-only / t = 0 forms) column blocks of rp columns.  For outer x inner rows:
+ *       dst[o][i][blk][dst_c0 + c] = src[o][i][blk][src_c0 + c],  c in [0, ncols);
+ *   a row is blocks * src_rp (blocks * dst_rp) floats, inner rows are adjacent, src_outer / dst_outer are the strides (in
+ *   floats) of the outer index.  zero_tail != 0: columns [dst_c0 + ncols, dst_rp) of every block are written as zeros.
+ *   Any extents and offsets (16-byte accesses when all are multiples of 4 and the bases aligned); ncols == 0 or no rows: no
+ *   launch.  One pass, no host reads, no allocation. */
+int mk_vcols_repack(const float* src, float* dst, long long outer, long long inner, int blocks, int ncols,
+                    long long src_outer, int src_rp, int src_c0, long long dst_outer, int dst_rp, int dst_c0,
+                    int zero_tail, void* stream);
 
 /* ---- longitude FFTs ----------------------------------------------------------
  * mk_rfft_rows: x[row][lat][lon] (f32|bf16)  ->  F-layout, modes m < mmax:

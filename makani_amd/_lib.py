@@ -58,6 +58,7 @@ _SIGS = {
     "mk_cgemm_split2_batched_ssq": ([C.POINTER(MkGemm), c_int, c_vp, c_vp], c_int),
     "mk_sgemm_presplit_batched": ([C.POINTER(MkGemm), c_vp, c_ll, c_ll, c_ll, c_int, c_vp, c_vp, c_int, c_vp], c_int),
     "mk_vlegendre": ([c_vp, c_vp, c_ll, c_ll, c_ll, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
+    "mk_vcols_repack": ([c_vp, c_vp, c_ll, c_ll, c_int, c_int, c_ll, c_int, c_int, c_ll, c_int, c_int, c_int, c_vp], c_int),
     "mk_rfft_rows": ([c_vp, c_int, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                       c_f, c_f, c_f, c_vp], c_int),
     "mk_irfft_rows": ([c_vp, c_vp, c_int, c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,

@@ -27,6 +27,14 @@
 //   mode 2  analysis, s only  in (u, v)  -> out s            out has TWO column blocks (re, im)
 //   mode 3  synthesis, t = 0  in s       -> out (u, v)       in  has TWO column blocks: the zero toroidal half is
 //                                                            neither stored nor multiplied (gradient of a scalar)
+//
+// The m-shard form (an azimuth rank of the h x w distributed pair, makani_amd/distributed.py): the launch covers `orders`
+// consecutive orders starting at tri_off.  Batch b is the GLOBAL order b + tri_off for the triangle (rows l < m skipped in 32-row
+// steps / k >= m) and the LOCAL order for everything that is addressed: limb planes (b * pl_batch), operands (b * b_batch,
+// b * c_batch) and band_lo[b] / band_hi[b] — the caller hands over the slices [tri_off, tri_off + orders) of all of them.
+// Orders are independent batches (no reduction crosses them, the XCD placement b % 8 is speed only), so a shard launch
+// performs the same products in the same order as the full launch does for those orders: bit-equal results, and the same
+// rows left unwritten (analysis never stores rows l < m; a synthesis band writes its zeros per order).
 #include "xsplit.h"
 
 namespace {

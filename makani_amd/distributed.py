@@ -9,6 +9,8 @@ forward   (w) planes<->lon all-to-all -> rFFT over full longitude, truncated
           Legendre analysis over full latitude with the local m-slice of the matrix
           (h) l<->planes all-to-all
 inverse   the same four exchanges in reverse order around synthesis and irFFT.
+The vector pair (``DistributedRealVectorSHT`` / ``DistributedInverseRealVectorSHT``) runs the same schedule on (u, v) pairs
+around ONE vector Legendre launch; its exchanges of the pair axis go through a repack kernel (see the section below).
 
 Differences from the reference's NCCL pattern, chosen for xGMI (point-to-point links, every
 peer pair has its own link): each exchange is ONE ``all_to_all`` on the internal F/S layouts
@@ -32,7 +34,7 @@ from . import _lib
 from . import comm as _comm
 from . import legendre as _leg
 from . import ops
-from .sht import RealSHT, InverseRealSHT
+from .sht import RealSHT, InverseRealSHT, RealVectorSHT, InverseRealVectorSHT
 
 def _size(group) -> int:
     return 1 if group is None else dist.get_world_size(group)
@@ -325,12 +327,23 @@ class HipBackend:
         return ops.legendre_synthesis(T, mat, nlat, m_off, lat_major=True, blocks=True)
 
     @staticmethod
-    def rfft(x4, mmax, w):
-        return ops.RfftFn.apply(x4, mmax, ops.round4(x4.shape[1]), w)
+    def rfft(x4, mmax, w, Cp=None):
+        """``Cp``: rows per leading index of ``x4`` in the F layout (the vector pair: (2, P, ...) with round32(P))"""
+        return ops.RfftFn.apply(x4, mmax, ops.round4(x4.shape[1]) if Cp is None else Cp, w)
 
     @staticmethod
-    def irfft(F, planes, nlon, dtype, w):
-        return ops.IrfftFn.apply(F, 1, planes, nlon, dtype, w)
+    def irfft(F, planes, nlon, dtype, w, B=1):
+        return ops.IrfftFn.apply(F, B, planes, nlon, dtype, w)
+
+    @staticmethod
+    def vlegendre(X, vm, mode, m_off):
+        """the vector Legendre launch on this azimuth rank's orders [m_off, m_off + M_loc) (modes: csrc/vlegendre.hip)"""
+        return ops.vector_legendre(X, vm, mode, m_off)
+
+    @staticmethod
+    def vcols_repack(src, dst, ncols, src_c0, dst_c0, zero_tail):
+        """one side of a pair-axis exchange on the column-block layout (csrc/vcols.hip)"""
+        ops.vcols_repack(src, dst, ncols, src_c0, dst_c0, zero_tail)
 
     @staticmethod
     def analysis(F, mat, matT, m_off):
@@ -464,6 +477,224 @@ class DistributedInverseRealSHT(InverseRealSHT, _DistBase):
         S = ops.ComplexToSFn.apply(c4, self.l_off, self.m_off)
         x = self.synthesis(S, c4.shape[0], c4.shape[1])
         return x.reshape(*lead, x.shape[-2], x.shape[-1])
+
+
+# --------------------------------------------------------------------------- #
+# the vector pair (``thd.DistributedRealVectorSHT`` / ``thd.DistributedInverseRealVectorSHT``)
+#
+# The same transpose-by-transpose schedule as the scalar pair above, four exchanges per transform.  The operand of the vector
+# Legendre kernel (csrc/vlegendre.hip) keeps its PAIRS in the last axis as [re/im][kind][Rp]: four column blocks (two for the
+# s-only / t = 0 forms), each padded to a multiple of 32.  An exchange that splits or joins pairs therefore touches every
+# block of every row.  The send slabs carry valid pairs only (one strided copy per peer); the receiving side is ONE pass of the
+# repack kernel (csrc/vcols.hip) per slab instead of cat + pad: arriving slabs land at their pair offset of the padded operand
+# — in a latitude range when latitudes are joined — and the pad columns are written as zeros.
+# The fused schedule of dist_pipeline.py is not extended to vectors (its sub-blocks come in 4s and latitude-major, the vector
+# kernel wants 32-column blocks), so there is nothing to fall back from and nothing is reported to dist_pipeline.FALLBACKS.
+# --------------------------------------------------------------------------- #
+def _vview(t, blocks):
+    """(a, b, 2, blocks / 2 * rp) -> the (a, b, blocks, rp) view of the column blocks"""
+    a, b = t.shape[:2]
+    return t.view(a, b, blocks, t.shape[2] * t.shape[3] // blocks)
+
+
+def _vpairs_exchange(x, blocks, gather, dim, dsizes, psizes, group):
+    """One exchange on the column-block layout.  ``dim`` (0 or 1) is the spatial / spectral axis with the shares ``dsizes``,
+    ``psizes`` the shares of the pairs.
+      gather      x (.., sum(dsizes) at dim, .., round32(psizes[me]) per block): split ``dim``, join the pairs
+                  -> (.., dsizes[me], .., round32(sum(psizes)))
+      not gather  x (.., dsizes[me], .., round32(sum(psizes))): split the pairs, join ``dim``
+                  -> (.., sum(dsizes), .., round32(psizes[me]))
+    Every rank enters the collective, also one that holds no pairs (its slabs are empty and it launches nothing)."""
+    n, me = dist.get_world_size(group), dist.get_rank(group)
+    assert len(dsizes) == n and len(psizes) == n and dim in (0, 1)
+    doff, poff = _offsets(dsizes), _offsets(psizes)
+    xv = _vview(x, blocks)
+    assert xv.shape[3] == ops.round32(psizes[me] if gather else poff[-1]) and xv.shape[dim] == (doff[-1] if gather else dsizes[me]), \
+        (tuple(x.shape), gather, dim, dsizes, psizes)
+    shape = list(xv.shape)
+    shape[dim] = dsizes[me] if gather else doff[-1]
+    shape[3] = ops.round32(poff[-1] if gather else psizes[me])
+    y = torch.empty(shape, dtype=x.dtype, device=x.device)
+    last = max([r for r in range(n) if psizes[r] > 0], default=-1)          # (gather) whose unpack zeroes the pad columns
+    repack = _BACKEND.vcols_repack
+    nothing = x.new_empty((0,))
+
+    def unpack(src, src_c0, r):
+        if gather:
+            repack(src, y, psizes[r], src_c0, poff[r], r == last)
+        else:
+            repack(src, y.narrow(dim, doff[r], dsizes[r]), psizes[me], src_c0, 0, True)
+
+    send, recv = [], []
+    for r in range(n):
+        src = xv.narrow(dim, doff[r], dsizes[r]) if gather else xv
+        ncols, c0 = (psizes[me], 0) if gather else (psizes[r], poff[r])
+        if r == me:                                  # this rank's own share never leaves: one pass from x into y
+            unpack(src, c0, me)
+            send.append(nothing)
+            recv.append(nothing)
+            continue
+        # pack: the peer's valid pairs only, no padding.  One strided copy; measured at the full-size h2 w2 shapes it takes
+        # 19 us where the repack kernel takes 24 (docs/LAB_NOTEBOOK.md 6.13), so the kernel serves the unpack side alone
+        send.append(src[..., c0:c0 + ncols].contiguous())
+        rshape = list(shape)
+        rshape[dim], rshape[3] = (dsizes[me], psizes[r]) if gather else (dsizes[r], psizes[me])
+        recv.append(torch.empty(rshape, dtype=x.dtype, device=x.device))
+    if n > 1:
+        _exchange(recv, send, group, count=True)
+    for r in range(n):
+        if r != me:
+            unpack(recv[r], 0, r)
+    return y.view(shape[0], shape[1], 2, blocks // 2 * shape[3])
+
+
+class _VPairsFn(torch.autograd.Function):
+    """pack -> all-to-all -> unpack; backward is the reverse exchange (as ``_TransposeFn``)"""
+
+    @staticmethod
+    def forward(ctx, x, blocks, gather, dim, dsizes, psizes, group):
+        ctx.meta = (blocks, gather, dim, dsizes, psizes, group)
+        return _vpairs_exchange(x.contiguous(), blocks, gather, dim, dsizes, psizes, group)
+
+    @staticmethod
+    def backward(ctx, gy):
+        blocks, gather, dim, dsizes, psizes, group = ctx.meta
+        return _vpairs_exchange(gy.contiguous(), blocks, not gather, dim, dsizes, psizes, group), None, None, None, None, None, None
+
+
+def _vpairs(x, blocks, gather, dim, dsizes, psizes, group):
+    """the exchange over ``group``; ``None`` = this direction is not split (a group of ONE rank still runs pack and unpack)"""
+    if group is None:
+        return x
+    return _VPairsFn.apply(x, blocks, gather, dim, list(dsizes), list(psizes), group)
+
+
+_VLEG_TRANSPOSED = {0: 1, 1: 0, 2: 3, 3: 2}
+
+
+class _VLegendreFn(torch.autograd.Function):
+    """the vector Legendre launch of mode 0-3 on this rank's orders; backward = the other direction with the transposed
+    matrices (``ops.VAnalysisFn`` / ``ops.VSynthesisFn``)"""
+
+    @staticmethod
+    def forward(ctx, X, vm, mode, m_off):
+        ctx.meta = (vm, mode, m_off)
+        return _BACKEND.vlegendre(X.contiguous(), vm, mode, m_off)
+
+    @staticmethod
+    def backward(ctx, g):
+        vm, mode, m_off = ctx.meta
+        return _BACKEND.vlegendre(g.contiguous(), vm, _VLEG_TRANSPOSED[mode], m_off), None, None, None
+
+
+class _DistVectorBase(_DistBase):
+    def _shard(self):
+        """keep the orders [m_off, m_off + m_loc) of the two latitude functions and of the polar band"""
+        self._setup_dist()
+        m0, m1 = self.m_off, self.m_off + self.m_shapes[self.comm_rank_azimuth]
+        for name in self._names:
+            setattr(self, name, getattr(self, name)[:, m0:m1].contiguous())
+        if self.band_lo is not None:
+            self.band_lo = self.band_lo[m0:m1].contiguous()
+            self.band_hi = self.band_hi[m0:m1].contiguous()
+        self._vm = None
+
+    def _local(self):
+        return self.lat_shapes[self.comm_rank_polar], self.lon_shapes[self.comm_rank_azimuth]
+
+
+class DistributedRealVectorSHT(RealVectorSHT, _DistVectorBase):
+    """``thd.DistributedRealVectorSHT``: local ``(..., 2, nlat_loc, nlon_loc)`` f32 | bf16 -> local ``(..., 2, l_loc, m_loc)``
+    complex64.  Keeps the m-slice of the two latitude functions (and of the polar band) this azimuth rank needs."""
+
+    def __init__(self, nlat, nlon, lmax=None, mmax=None, grid="equiangular", norm="ortho", csphase=True):
+        super().__init__(nlat, nlon, lmax, mmax, grid, norm, csphase)
+        self._shard()
+
+    def analysis(self, xc: torch.Tensor, s_only: bool = False, legendre_phase: bool = False) -> torch.Tensor:
+        """(2, P, nlat_loc, nlon_loc), component outermost -> S-layout (l_loc, m_loc, 2, 2 Rp), Rp = round32(P); ``s_only``:
+        (l_loc, m_loc, 2, Rp).  ``legendre_phase``: stop after the Legendre launch and hand over its operand
+        (lmax, m_loc, 2, 2 round32(P_h)) — all degrees of this polar rank's share P_h of the pairs — which
+        ``DistributedInverseRealVectorSHT.synthesis(legendre_phase=True)`` takes: the round trip skips both polar exchanges."""
+        hl, wl = self._local()
+        if xc.dim() != 4 or xc.shape[0] != 2 or xc.shape[-2] != hl or xc.shape[-1] != wl:
+            raise ValueError(f"expected local shape (2, P, {hl}, {wl}), got {tuple(xc.shape)}")
+        P = xc.shape[1]
+        pw, ph = self._plane_shapes(P)
+        Pw = pw[self.comm_rank_azimuth]
+        hg, wg = polar_group(), azimuth_group()
+        # (w) pairs <-> lon
+        x = transpose(xc, 1, pw, 3, self.lon_shapes, wg)                                    # (2, P_w, hl, nlon)
+        if Pw > 0:
+            F = _BACKEND.rfft(x.contiguous(), self.mmax, self._w, Cp=ops.round32(Pw))      # (M, hl, 2, 2 round32(P_w))
+        else:                                                                               # no pairs here: nothing to launch
+            F = x.reshape(self.mmax, hl, 2, 0)
+            F = F.float() if F.dtype == torch.bfloat16 else F
+        # (w) m <-> pairs
+        F = _vpairs(F, 4, True, 0, self.m_shapes, pw, wg)                                   # (M_loc, hl, 2, 2 round32(P))
+        # (h) pairs <-> lat
+        F = _vpairs(F, 4, False, 1, self.lat_shapes, ph, hg)                                # (M_loc, nlat, 2, 2 round32(P_h))
+        S = _VLegendreFn.apply(F, self._mats(), 2 if s_only else 0, self.m_off)             # (L, M_loc, 2, 2 round32(P_h))
+        if legendre_phase:
+            return S
+        # (h) l <-> pairs
+        return _vpairs(S, 2 if s_only else 4, True, 0, self.l_shapes, ph, hg)               # (L_loc, M_loc, 2, 2 round32(P))
+
+    @torch.compiler.disable(recursive=True)
+    @_lib.device_guard
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"DistributedRealVectorSHT (HIP) supports float32 / bfloat16 input, got {x.dtype}")
+        xc, lead = self._pairs_first(x, self._local())
+        S = self.analysis(xc)
+        c = ops.VSToComplexFn.apply(S, 2, xc.shape[1], self.l_off, self.m_off)
+        return c.transpose(0, 1).reshape(*lead, 2, c.shape[-2], c.shape[-1])
+
+
+class DistributedInverseRealVectorSHT(InverseRealVectorSHT, _DistVectorBase):
+    """``thd.DistributedInverseRealVectorSHT``: local ``(..., 2, l_loc, m_loc)`` complex64 -> local
+    ``(..., 2, nlat_loc, nlon_loc)`` float32."""
+
+    def __init__(self, nlat, nlon, lmax=None, mmax=None, grid="equiangular", norm="ortho", csphase=True):
+        super().__init__(nlat, nlon, lmax, mmax, grid, norm, csphase)
+        self._shard()
+
+    def synthesis(self, S: torch.Tensor, P: int, out_dtype=torch.float32, t_zero: bool = False,
+                  legendre_phase: bool = False) -> torch.Tensor:
+        """S-layout (l_loc, m_loc, 2, 2 Rp) -> (2, P, nlat_loc, nlon_loc); ``t_zero``: S is (l_loc, m_loc, 2, Rp), the spheroidal
+        coefficients alone.  ``legendre_phase``: S is the Legendre-phase operand (lmax, m_loc, 2, 2 round32(P_h)) as
+        ``DistributedRealVectorSHT.analysis(legendre_phase=True)`` hands it over."""
+        hl, wl = self._local()
+        pw, ph = self._plane_shapes(P)
+        Pw = pw[self.comm_rank_azimuth]
+        hg, wg = polar_group(), azimuth_group()
+        if not legendre_phase:
+            # (h) pairs <-> l
+            S = _vpairs(S, 2 if t_zero else 4, False, 0, self.l_shapes, ph, hg)             # (L, M_loc, 2, 2 round32(P_h))
+        F = _VLegendreFn.apply(S, self._mats(), 3 if t_zero else 1, self.m_off)             # (M_loc, nlat, 2, 2 round32(P_h))
+        # (h) lat <-> pairs
+        F = _vpairs(F, 4, True, 1, self.lat_shapes, ph, hg)                                 # (M_loc, hl, 2, 2 round32(P))
+        # (w) pairs <-> m
+        F = _vpairs(F, 4, False, 0, self.m_shapes, pw, wg)                                  # (M, hl, 2, 2 round32(P_w))
+        if Pw > 0:
+            x = _BACKEND.irfft(F.contiguous(), Pw, self.nlon, out_dtype, self._w, B=2)      # (2, P_w, hl, nlon)
+        else:
+            x = F.reshape(2, 0, hl, self.nlon).to(out_dtype)
+        # (w) lon <-> pairs
+        return transpose(x, 3, self.lon_shapes, 1, pw, wg)                                  # (2, P, hl, wl)
+
+    @torch.compiler.disable(recursive=True)
+    @_lib.device_guard
+    def forward(self, c: torch.Tensor) -> torch.Tensor:
+        if c.dtype != torch.complex64:
+            raise TypeError(f"DistributedInverseRealVectorSHT (HIP) supports complex64 input, got {c.dtype}")
+        ll, ml = self.l_shapes[self.comm_rank_polar], self.m_shapes[self.comm_rank_azimuth]
+        if c.shape[-2] != ll or c.shape[-1] != ml:
+            raise ValueError(f"expected local shape (..., 2, {ll}, {ml}), got {tuple(c.shape)}")
+        cc, lead = self._pairs_first(c, (ll, ml))
+        S = ops.VComplexToSFn.apply(cc, ops.round32(cc.shape[1]), self.l_off, self.m_off)
+        x = self.synthesis(S, cc.shape[1])
+        return x.transpose(0, 1).reshape(*lead, 2, x.shape[-2], x.shape[-1])
 
 
 class DistributedInstanceNorm2d(nn.Module):

@@ -633,13 +633,16 @@ class _EnsembleGridLoss(_EnsembleLoss):
     def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
                  ensemble_distributed, ensemble_weights, alpha, eps):
         if spatial_distributed or ensemble_distributed:
+            import torch.distributed as dist
             from . import comm as _comm
             _comm.autodetect()
-            if (spatial_distributed and _comm.is_distributed("spatial") and _comm.get_size("spatial") > 1) or \
-                    (ensemble_distributed and _comm.is_distributed("ensemble") and _comm.get_size("ensemble") > 1):
-                raise NotImplementedError(f"{type(self).__name__}: the distributed vector transforms are not built yet "
-                                          "(spatial_distributed / ensemble_distributed with a group larger than one)")
-        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, False, False)          # serial only
+            split = (spatial_distributed and _comm.is_distributed("spatial") and _comm.get_size("spatial") > 1) or \
+                (ensemble_distributed and _comm.is_distributed("ensemble") and _comm.get_size("ensemble") > 1)
+            if split and not (dist.is_available() and dist.is_initialized()):
+                raise NotImplementedError(f"{type(self).__name__}: spatial_distributed / ensemble_distributed with a group larger than "
+                                          "one needs an initialised torch.distributed process group in this process (the distributed "
+                                          "vector transforms and the ensemble exchange run over it)")
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
         if tuple(crop_shape) != tuple(img_shape):
             raise NotImplementedError("the vector-transform losses score the whole sphere (crop_shape == img_shape)")
         if crps_type not in ("skillspread", "naive skillspread") and alpha < 1.0:
@@ -661,11 +664,30 @@ class _EnsembleGridLoss(_EnsembleLoss):
         if self.crps_type not in ("cdf", "skillspread", "gauss"):              # what the reference's forward knows
             raise ValueError(f"Unknown CRPS crps_type {self.crps_type}")
         B, E, Cc, H, W = forecasts.shape
-        if E == 1:
+        if E == 1 and not self.ensemble_distributed:              # (the quadrature sums over the spatial group itself)
             return self.quadrature.lp(forecasts.squeeze(1), observations, spatial_weights, 1.0).reshape(B, Cc)
+        if self.spatial_distributed or self.ensemble_distributed:
+            # the score stage of CRPSLoss on this rank's points with the local quadrature weights: members <-> a share of the
+            # points over the ensemble group, then the SUM over the ensemble and the spatial group (crps_loss.py:775-841)
+            f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
+            crps = CrpsFn.apply(f.unsqueeze(-1), o.unsqueeze(-1), q, w.unsqueeze(-1) if w is not None else None,
+                                _CRPS_TYPES[self.crps_type], self.alpha, self.eps, _ens_w(self.ensemble_weights, f.shape[1], self.crps_type))
+            return self._sum_shares(crps, groups)
         w = spatial_weights.expand(B, Cc, H, W) if spatial_weights is not None else None
         return CrpsFn.apply(forecasts, observations, self.quad_weight_split.reshape(-1), w, _CRPS_TYPES[self.crps_type], self.alpha,
                             self.eps, _ens_w(self.ensemble_weights, E, self.crps_type))
+
+    def _transforms(self, lmax, grid_type, forward_vector):
+        """(forward transform, inverse vector transform) on the whole sphere, or on this rank's shard of it"""
+        nlat, nlon = self.img_shape
+        kw = dict(lmax=lmax, mmax=lmax, grid=grid_type)
+        if self.spatial_distributed:
+            from . import distributed as thd
+            fw = (thd.DistributedRealVectorSHT if forward_vector else thd.DistributedRealSHT)(nlat, nlon, **kw)
+            return fw, thd.DistributedInverseRealVectorSHT(fw.nlat, fw.nlon, **kw)
+        from .sht import RealSHT, RealVectorSHT, InverseRealVectorSHT
+        fw = (RealVectorSHT if forward_vector else RealSHT)(nlat, nlon, **kw)
+        return fw, InverseRealVectorSHT(fw.nlat, fw.nlon, **kw)
 
 
 class GradientCRPSLoss(_EnsembleGridLoss):
@@ -673,7 +695,8 @@ class GradientCRPSLoss(_EnsembleGridLoss):
     surface gradient of every channel — ``absolute=True``: of its magnitude, (B, C); ``False``: of both components, (B, 2 C) in
     the order (c, component).  Scalar analysis (HIP SHT), then the vector synthesis with a ZERO toroidal part
     (``InverseRealVectorSHT.synthesis(t_zero=True)``: nothing is stored or multiplied for it), in fp32 whatever the autocast
-    state; score and quadrature are the kernels of ``CRPSLoss``.  Serial only."""
+    state; score and quadrature are the kernels of ``CRPSLoss``.  ``spatial_distributed`` / ``ensemble_distributed`` as in
+    ``CRPSLoss``: the transforms are the distributed pair on this rank's shard of the sphere and this rank's members."""
 
     def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
                  channel_names: List[str], grid_type: str, lmax: Optional[int] = None, crps_type: str = "skillspread",
@@ -682,10 +705,8 @@ class GradientCRPSLoss(_EnsembleGridLoss):
                  eps: Optional[float] = 1.0e-6, **kwargs):
         super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
                          ensemble_distributed, ensemble_weights, alpha, eps)
-        from .sht import RealSHT, InverseRealVectorSHT
         self.absolute = absolute
-        self.sht = RealSHT(*img_shape, lmax=lmax, mmax=lmax, grid=grid_type)
-        self.ivsht = InverseRealVectorSHT(self.sht.nlat, self.sht.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+        self.sht, self.ivsht = self._transforms(lmax, grid_type, False)
 
     @property
     def n_channels(self):
@@ -733,7 +754,8 @@ class VortDivCRPSLoss(_EnsembleGridLoss):
     """``VortDivCRPSLoss`` of ``makani/utils/losses/crps_loss.py:847-1019`` ("ensemble_vort_div_crps"): every (u, v) pair of the
     channel list goes through the vector transform round trip (fp32, autocast off) and is scattered back, the other channels
     pass through; the ensemble CRPS of the result, (B, C).  Analysis and synthesis are chained on the internal S layout (no
-    complex64 tensor in between).  Serial only."""
+    complex64 tensor in between).  ``spatial_distributed`` / ``ensemble_distributed`` as in ``CRPSLoss``; on a split sphere the round trip
+    hands the Legendre-phase operand from the analysis to the synthesis and skips both polar exchanges."""
 
     def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
                  channel_names: List[str], grid_type: str, crps_type: str = "skillspread",
@@ -742,10 +764,8 @@ class VortDivCRPSLoss(_EnsembleGridLoss):
                  lmax: Optional[int] = None, **kwargs):
         super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, crps_type, spatial_distributed,
                          ensemble_distributed, ensemble_weights, alpha, eps)
-        from .sht import RealVectorSHT, InverseRealVectorSHT
         self.register_buffer("wind_chans", torch.LongTensor(get_wind_channels(channel_names)), persistent=False)
-        self.vsht = RealVectorSHT(*img_shape, lmax=lmax, mmax=lmax, grid=grid_type)
-        self.isht = InverseRealVectorSHT(self.vsht.nlat, self.vsht.nlon, lmax=lmax, mmax=lmax, grid=grid_type)
+        self.vsht, self.isht = self._transforms(lmax, grid_type, True)
 
     def average_wind_weights(self, chw):
         wind = self.wind_chans.to(chw.device)
@@ -766,8 +786,12 @@ class VortDivCRPSLoss(_EnsembleGridLoss):
         N, Cc, H, W = x.shape
         wind = x[:, self.wind_chans].reshape(N * (Cw // 2), 2, H, W)
         xc = wind.transpose(0, 1).contiguous()                                      # (2, P, H, W): component outermost
-        S = self.vsht.analysis(xc)
-        back = self.isht.synthesis(S, xc.shape[1])                                  # (2, P, H, W)
+        if self.spatial_distributed:            # the l <-> pairs exchange of the analysis and its mirror in the synthesis cancel
+            S = self.vsht.analysis(xc, legendre_phase=True)
+            back = self.isht.synthesis(S, xc.shape[1], legendre_phase=True)
+        else:
+            S = self.vsht.analysis(xc)
+            back = self.isht.synthesis(S, xc.shape[1])                              # (2, P, H, W)
         back = back.transpose(0, 1).reshape(N, Cw, H, W)
         return x.index_copy(1, self.wind_chans, back)
 

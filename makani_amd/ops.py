@@ -865,9 +865,10 @@ class VectorMats:
         self.nat, self.tr, self.band, self.L, self.nlat = nat, tr, band, L, nlat
 
 
-def vector_legendre(X: torch.Tensor, vm: VectorMats, mode: int) -> torch.Tensor:
+def vector_legendre(X: torch.Tensor, vm: VectorMats, mode: int, m_off: int = 0) -> torch.Tensor:
     """mode 0: F (M, nlat, 2, 2 Rp) -> S (L, M, 2, 2 Rp);  1: S -> F;  2: F -> S (L, M, 2, Rp), spheroidal part only;
-    3: S (L, M, 2, Rp) -> F with a zero toroidal part (see include/makani_amd.h, mk_vlegendre)."""
+    3: S (L, M, 2, Rp) -> F with a zero toroidal part (see include/makani_amd.h, mk_vlegendre).  ``m_off``: the m-shard form —
+    M counts the orders [m_off, m_off + M) and ``vm`` holds the matrices and bands of exactly those orders."""
     gm = gemm_mode()
     if gm == "fp32":
         raise NotImplementedError("the vector Legendre kernels run on the split-bf16 engine (MAKANI_AMD_GEMM=auto, x6 or x3)")
@@ -887,14 +888,35 @@ def vector_legendre(X: torch.Tensor, vm: VectorMats, mode: int) -> torch.Tensor:
         out = torch.empty((M, vm.nlat, 2, 2 * Rp), dtype=torch.float32, device=X.device)
         m0, m1, rows, K = vm.nat[0], vm.nat[1], vm.nlat, L
     assert m0.shape[0] == M and Rp % 32 == 0
+    if out.numel() == 0:                                     # a rank that holds no pairs (or no orders) in this phase: no launch
+        return out
     p0, p1 = limb_planes(m0), limb_planes(m1)
     lo, hi = vm.band if vm.band is not None else (None, None)
     prods = 1 if mode == 3 else 2
     with _timed(f"vlegendre_{'analysis' if ana else 'synthesis'}_k{vm.nlat}", flops=2.0 * prods * out.shape[-1] * 2 * vm.nlat * vm.L * M,
                 nbytes=4.0 * (X.numel() + out.numel() + 2 * M * vm.L * vm.nlat)):
         check(lib().mk_vlegendre(ptr(p0), ptr(p1), p0.stride(0), p0.stride(1), p0.stride(2), limbs, ptr(X), ptr(out), mode,
-                                 rows, K, M, Rp, 0, ptr(lo), ptr(hi), stream()), "mk_vlegendre")
+                                 rows, K, M, Rp, m_off, ptr(lo), ptr(hi), stream()), "mk_vlegendre")
     return out
+
+
+def vcols_repack(src: torch.Tensor, dst: torch.Tensor, ncols: int, src_c0: int = 0, dst_c0: int = 0, zero_tail: bool = False):
+    """``dst[..., dst_c0:dst_c0 + ncols] = src[..., src_c0:src_c0 + ncols]`` for (outer, inner, blocks, rp) fp32 views whose last
+    three dims are dense (the outer stride is free: a slab of a latitude range) and, with ``zero_tail``,
+    ``dst[..., dst_c0 + ncols:] = 0`` — one pass, one launch (csrc/vcols.hip); ``ncols == 0`` or no rows: nothing is launched"""
+    assert src.dim() == 4 and dst.dim() == 4 and src.shape[:3] == dst.shape[:3], (src.shape, dst.shape)
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32
+    outer, inner, blocks, srp = src.shape
+    drp = dst.shape[3]
+    assert 0 <= src_c0 and src_c0 + ncols <= srp and 0 <= dst_c0 and dst_c0 + ncols <= drp
+    if outer == 0 or inner == 0 or ncols == 0:
+        return
+    for t in (src, dst):
+        rp = t.shape[3]
+        assert t.stride(3) == 1 and t.stride(2) == rp and (inner == 1 or t.stride(1) == blocks * rp) and \
+            (outer == 1 or t.stride(0) >= inner * blocks * rp), (t.shape, t.stride())
+    check(lib().mk_vcols_repack(ptr(src), ptr(dst), outer, inner, blocks, ncols, src.stride(0), srp, src_c0, dst.stride(0), drp,
+                                dst_c0, 1 if zero_tail else 0, stream()), "mk_vcols_repack")
 
 
 class VAnalysisFn(torch.autograd.Function):
@@ -928,25 +950,26 @@ class VSToComplexFn(torch.autograd.Function):
     """S (L, M, 2, B * Cp) -> complex64 (B, Cc, L, M) for any row padding Cp (the scalar pair's Cp is round4(Cc))"""
 
     @staticmethod
-    def forward(ctx, S, B, Cc):
+    def forward(ctx, S, B, Cc, l_off=0, m_off=0):
+        """l_off / m_off: first degree / order of this rank's shard (entries with l < m are exact zeros)"""
         ctx.Cp = S.shape[3] // B
-        return s_to_complex(S, B, Cc)
+        return s_to_complex(S, B, Cc, l_off, m_off)
 
     @staticmethod
     def backward(ctx, gc):
-        return complex_to_s(gc, ctx.Cp), None, None
+        return complex_to_s(gc, ctx.Cp), None, None, None, None
 
 
 class VComplexToSFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, c, Cp):
-        ctx.meta = c.shape[:2]
+    def forward(ctx, c, Cp, l_off=0, m_off=0):
+        ctx.meta = (*c.shape[:2], l_off, m_off)
         return complex_to_s(c, Cp)
 
     @staticmethod
     def backward(ctx, gS):
-        B, Cc = ctx.meta
-        return s_to_complex(gS.contiguous(), B, Cc), None
+        B, Cc, l_off, m_off = ctx.meta
+        return s_to_complex(gS.contiguous(), B, Cc, l_off, m_off), None, None, None
 
 
 # --------------------------------------------------------------------------- #
