@@ -592,6 +592,45 @@ int mk_resample_bwd(const void* gy, void* gx, int dtype, const int* lat_off, con
                     const int* lon_off, const int* lon_p, const float* lon_wt, const int* pole_off, const int* pole_t,
                     const float* pole_wt, int planes, int nlat_in, int nlon_in, int nlat_out, int nlon_out, void* stream);
 
+/* ---- Preprocessor2D around the network (csrc/preproc.hip; makani/models/preprocessor.py:412-687,1018-1036) ----------------
+ * T = n_history + 1 time levels of J = C + U + N channels each: C = WC / T of the window win (B, WC, HW), U of the cached
+ * unpredicted features unp (B, T, U, HW), N of the noise noi (B, T, N, HW); f32 | bf16 each, read in place (unp / noi may be
+ * NULL when U / N is 0).  omega[t][p] = wt[t] q[p] with q (HW) the normalised quadrature weights and wt (T) the history weights.
+ * Statistics mu, sigma (B, J) are fp32.  Workspaces ws are sized with mk_prep_chunks(HW); chunk sums are added in chunk order
+ * (no atomics): repeats are bit-identical.  16-byte accesses when HW is a multiple of 4 and every pointer is 16-byte aligned,
+ * scalar ones otherwise.  B J, T J + S, B <= 65535.
+ *   mk_prep_stats:      mu = sum omega v, sigma = sqrt(sum omega (v - mu)^2); per chunk (weight, mean, M2) about a pivot, merged
+ *                       by Chan's formula in fp64.  tri (B, J, 3) fp64 = (sum omega, mean, M2), what ranks of a split sphere
+ *                       exchange; mu / sigma or tri may be NULL.  ws: B J mk_prep_chunks(HW) 4 floats.
+ *   mk_prep_assemble:   out (B, T J + S, HW): channel t J + j = (v - mu[b][j]) / sigma[b][j], channel T J + s = stat[s] (S, HW);
+ *                       mu = sigma = NULL: no normalisation.
+ *   mk_prep_finish:     y = (yn - bias) sigma[b][c] + mu[b][c]; yn, y (B, Cout, HW) of one dtype, bias (Cout, HW) f32, the
+ *                       statistics (B, J) with J >= Cout; bias, mu, sigma optional each.
+ *   mk_prep_bwd_sums:   G (2, B, J): G[0] = gmu - (sum g) / sigma, G[1] = gsig - (sum g xn) / sigma with g (B, T J + S, HW) the
+ *                       gradient of out, xn recomputed, gmu / gsig (B, J) optional.  ws: B J mk_prep_chunks(HW) 2 floats.
+ *                       need: bit 0 the window's channels, bit 1 the noise channels; channels without a gradient tensor are
+ *                       not read (their sums are 0), so unp may be NULL here and in mk_prep_bwd_apply, noi when it gets none.
+ *   mk_prep_bwd_apply:  dv = g / sigma + omega (G[0] + xn G[1]) into dwin (shape of win) and, when given, dnoi (shape of noi);
+ *                       g or G may be NULL; mu = sigma = NULL: dv = g.
+ *   mk_prep_finish_bwd: gmu[b][c] = sum g, gsig[b][c] = sum g (yn - bias), written to index b J + c.  ws: B Cout chunks 2 floats. */
+int mk_prep_chunks(long long HW);
+int mk_prep_stats(const void* win, int win_dtype, const void* unp, int unp_dtype, const void* noi, int noi_dtype, const float* q,
+                  const float* wt, float* mu, float* sigma, double* tri, float* ws, int B, int T, int WC, int U, int N, long long HW,
+                  void* stream);
+int mk_prep_assemble(const void* win, int win_dtype, const void* unp, int unp_dtype, const void* noi, int noi_dtype, const void* stat,
+                     int stat_dtype, const float* mu, const float* sigma, void* out, int out_dtype, int B, int T, int WC, int U, int N,
+                     int S, long long HW, void* stream);
+int mk_prep_finish(const void* yn, int dtype, const float* bias, const float* mu, const float* sigma, void* y, int B, int Cout, int J,
+                   long long HW, void* stream);
+int mk_prep_bwd_sums(const void* g, int g_dtype, const void* win, int win_dtype, const void* unp, int unp_dtype, const void* noi,
+                     int noi_dtype, const float* mu, const float* sigma, const float* gmu, const float* gsig, float* G, float* ws, int B,
+                     int T, int WC, int U, int N, int S, int need, long long HW, void* stream);
+int mk_prep_bwd_apply(const void* g, int g_dtype, const void* win, int win_dtype, const void* unp, int unp_dtype, const void* noi,
+                      int noi_dtype, const float* q, const float* wt, const float* mu, const float* sigma, const float* G, void* dwin,
+                      void* dnoi, int B, int T, int WC, int U, int N, int S, long long HW, void* stream);
+int mk_prep_finish_bwd(const void* g, int g_dtype, const void* yn, int yn_dtype, const float* bias, float* gmu, float* gsig, float* ws,
+                       int B, int Cout, int J, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

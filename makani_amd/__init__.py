@@ -14,6 +14,7 @@ from .metrics import (GeometricL1, GeometricRMSE, GeometricACC, GeometricSpread,
 from .stepper import MultiStepWrapper, SingleStepWrapper
 from .disco import DiscreteContinuousConvS2, ResampleS2
 from .fcn3 import AtmoSphericNeuralOperatorNet
+from .preprocessor import Preprocessor2D
 from .noise import BaseNoiseS2, IsotropicGaussianRandomFieldS2, DiffusionNoiseS2, DummyNoiseS2, InputNoise, build_noise, noise_seed_reflect
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
@@ -26,4 +27,4 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
            "deterministic_sums",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
-           "noise_seed_reflect"]
+           "noise_seed_reflect", "Preprocessor2D"]

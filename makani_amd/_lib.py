@@ -141,6 +141,17 @@ _SIGS = {
     "mk_quad_lp_chunks": ([c_ll], c_int),
     "mk_quad_lp_fwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_int, c_f, c_vp], c_int),
     "mk_quad_lp_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_int, c_f, c_vp], c_int),
+    "mk_prep_chunks": ([c_ll], c_int),
+    "mk_prep_stats": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll,
+                       c_vp], c_int),
+    "mk_prep_assemble": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_int, c_ll, c_vp], c_int),
+    "mk_prep_finish": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_prep_bwd_sums": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
+                          c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_prep_bwd_apply": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
+                           c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_prep_finish_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
 }
 
 EXPORTS = sorted(list(_SIGS) + ["mk_last_error"])

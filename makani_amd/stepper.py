@@ -2,10 +2,11 @@
 ``--multistep_count > 1`` (``makani/models/stepper.py:176-345``).
 
 makani's wrapper threads every step through ``Preprocessor2D`` (history normalisation, unpredicted / static feature
-channels, input noise, bias correction — the data pipeline, SURVEY §2: OUT).  In the north-star configuration all
-of those stages are identities (``history_normalization_mode: "none"``, no zenith / orography / land-mask channels,
-no noise), and what remains is the part that decides the cost of a rollout on the GPU, plus the one stage the ensemble
-recipes cannot do without — the input noise (``input_noise=``, a ``makani_amd.noise.InputNoise``):
+channels, input noise, bias correction).  That stage is ``makani_amd.preprocessor.Preprocessor2D`` and comes in through the
+``preprocessor=`` keyword (last paragraph).  Without it — the north-star configuration, where all of those stages are identities
+(``history_normalization_mode: "none"``, no zenith / orography / land-mask channels, no noise) — what remains is the part that
+decides the cost of a rollout on the GPU, plus the one stage the ensemble recipes cannot do without, the input noise
+(``input_noise=``, a ``makani_amd.noise.InputNoise``):
 
 * the loop itself — ``n_future + 1`` network calls, the prediction of step k appended to the history window that
   feeds step k+1 (``stepper.py:236-281``, ``preprocessor.py:341-410``), all steps concatenated along the channel axis
@@ -25,6 +26,15 @@ recipes cannot do without — the input noise (``input_noise=``, a ``makani_amd.
 
 Evaluation mode performs ONE step (``stepper.py:286-313``): inference drives the rollout itself; the noise state is sized to
 the call's batch there.
+
+With ``preprocessor=`` (a ``makani_amd.preprocessor.Preprocessor2D``) both wrappers run the reference's full order
+(``stepper.py:76-136,224-315``): ``update_internal_state``; per step ``preprocessor.assemble`` (unpredicted and noise channels,
+history statistics, normalisation, static channels: two launches) → network (checkpointed as above; the preprocessor stays
+outside the checkpoint) → ``preprocessor.finish`` (bias correction, de-normalisation with the statistics of THIS step: one
+launch); then ``update_internal_state(replace_state=False)`` and ``preprocessor.append_history(window, pred, step)``, which also
+slides the cached unpredicted input forward.  The statistics are differentiable: without push-forward mode the gradient reaches
+earlier steps through mean and std.  ``from_params`` of both wrappers is unchanged and still refuses the preprocessor's keys; the
+route for a recipe that has them is ``Wrapper(model, ..., preprocessor=Preprocessor2D.from_params(params, ...))``.
 """
 import torch
 import torch.nn as nn
@@ -45,12 +55,22 @@ class MultiStepWrapper(nn.Module):
 
     ``forward(inp)``: ``inp`` (B, (n_history + 1)·C, H, W) → (B, (n_future + 1)·C_out, H, W) in training mode,
     (B, C_out, H, W) in evaluation mode.  ``update_state`` / ``replace_state`` steer the state of ``input_noise`` (an
-    ``InputNoise``, e.g. ``InputNoise.from_params(params)``); without one they are accepted for signature compatibility."""
+    ``InputNoise``, e.g. ``InputNoise.from_params(params)``); without one they are accepted for signature compatibility.
+    ``preprocessor=`` (a ``Preprocessor2D``, e.g. ``Preprocessor2D.from_params(params, ...)``) puts the reference's whole
+    preprocessing around every step (module docstring); it owns the noise, so giving both keywords is a ``ValueError``.
+    ``from_params`` does not build one and keeps refusing the preprocessor's keys."""
 
-    def __init__(self, model, n_future=0, n_history=0, push_forward=False, multistep_checkpoint=False, input_noise=None):
+    def __init__(self, model, n_future=0, n_history=0, push_forward=False, multistep_checkpoint=False, input_noise=None,
+                 preprocessor=None):
         super().__init__()
         if n_future < 0 or n_history < 0:
             raise ValueError(f"n_future ({n_future}) and n_history ({n_history}) must be >= 0")
+        if preprocessor is not None and input_noise is not None:
+            raise ValueError("preprocessor= and input_noise= are both given: the noise belongs to the preprocessor "
+                             "(Preprocessor2D(..., input_noise=...))")
+        if preprocessor is not None and preprocessor.n_history != int(n_history):
+            raise ValueError(f"the preprocessor carries n_history = {preprocessor.n_history}, the rollout {int(n_history)}")
+        self.preprocessor = preprocessor
         self.model = model
         self.n_future, self.n_history = int(n_future), int(n_history)
         self.push_forward_mode = bool(push_forward)
@@ -104,7 +124,31 @@ class MultiStepWrapper(nn.Module):
             return checkpoint(self.model, x, use_reentrant=False, preserve_rng_state=True)
         return self.model(x)
 
+    def _forward_preprocessed(self, inp, update_state, replace_state):
+        """the reference's ``_forward_train`` / ``_forward_eval`` (``stepper.py:224-315``) around ``self.preprocessor``"""
+        pre = self.preprocessor
+        if not self.training:
+            if update_state:
+                pre.update_internal_state(replace_state=replace_state, batch_size=inp.shape[0])
+            return pre.finish(self.model(pre.assemble(inp)))
+        if update_state:
+            pre.update_internal_state(replace_state=replace_state)
+        result = []
+        window = inp
+        for step in range(self.n_future + 1):
+            if self.push_forward_mode:
+                window = window.detach()
+            pred = pre.finish(self._step(pre.assemble(window)))          # (statistics of this step: de-normalise before they move on)
+            result.append(pred)
+            if step == self.n_future:
+                break
+            pre.update_internal_state(replace_state=False)
+            window = pre.append_history(window, pred, step)
+        return torch.cat(result, dim=1)
+
     def forward(self, inp, update_state=True, replace_state=True):
+        if self.preprocessor is not None:
+            return self._forward_preprocessed(inp, update_state, replace_state)
         noise = self.input_noise
         if not self.training:
             if noise is None:
@@ -130,14 +174,24 @@ class MultiStepWrapper(nn.Module):
 
 class SingleStepWrapper(nn.Module):
     """one step; ``encode_process`` forwarded when the network has it (``stepper.py:50-173``).  With ``input_noise`` (an
-    ``InputNoise``) the state is advanced at the call's batch size when ``update_state`` says so, then appended / added."""
+    ``InputNoise``) the state is advanced at the call's batch size when ``update_state`` says so, then appended / added.  With
+    ``preprocessor`` (a ``Preprocessor2D``, which then owns the noise) ``forward`` is ``finish(model(assemble(inp)))`` and
+    ``encode_process`` shares the same ``_preprocess``."""
 
-    def __init__(self, model, input_noise=None):
+    def __init__(self, model, input_noise=None, preprocessor=None):
         super().__init__()
+        if preprocessor is not None and input_noise is not None:
+            raise ValueError("preprocessor= and input_noise= are both given: the noise belongs to the preprocessor "
+                             "(Preprocessor2D(..., input_noise=...))")
         self.model = model
         self.input_noise = input_noise
+        self.preprocessor = preprocessor
 
     def _preprocess(self, inp, update_state, replace_state):
+        if self.preprocessor is not None:
+            if update_state:
+                self.preprocessor.update_internal_state(replace_state=replace_state, batch_size=inp.shape[0])
+            return self.preprocessor.assemble(inp)
         if self.input_noise is None:
             return inp
         if update_state:
@@ -145,7 +199,8 @@ class SingleStepWrapper(nn.Module):
         return self.input_noise(inp)
 
     def forward(self, inp, update_state=True, replace_state=True):
-        return self.model(self._preprocess(inp, update_state, replace_state))
+        y = self.model(self._preprocess(inp, update_state, replace_state))
+        return y if self.preprocessor is None else self.preprocessor.finish(y)
 
     def encode_process(self, inp, update_state=True, replace_state=True):
         if not hasattr(self.model, "encode_process"):

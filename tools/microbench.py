@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -556,6 +556,72 @@ def noise_shard():
               f"same size {tw[0] * 1e3:6.1f} / {tw[3] * 1e3:6.1f} / {tw[6] * 1e3:6.1f} us = {nbytes / tw[3] / 1e6:7.1f} GB/s | "
               f"shard / whole {ts[3] / tw[3]:5.2f}", flush=True)
         del box, whole
+
+
+def preproc():
+    """Preprocessor2D's fused stages (csrc/preproc.hip) at 721 x 1440, B = 1, C = 73, U = 1, S = 3, fp32, forward only, modes "none"
+    and "mean", n_history 0 and 1, beside the torch composition of the reference's operations (cat, weighted quadrature sums, tile,
+    sub, div, cat; sub, mul, add) on the same tensors, the two timed in turn over three rounds, every timing over a window of at
+    least 0.5 s.  Algorithmic bytes: statistics one read of the sources; assemble one read of sources and static planes plus one
+    write of the network input; finish one read of yn and the bias field plus one write."""
+    PEAK = 8.0e12
+    H, W, B, C, U, S = 721, 1440, 1, 73, 1, 3
+    N = H * W
+    rate = lambda nbytes, ms: f"{nbytes / (ms * 1e-3) / PEAK * 100:5.1f} % of the HBM roof"
+
+    def timed(fn):
+        once = max(timeit(fn, reps=3, warm=2), 1e-3)
+        return timeit(fn, reps=max(5, int(math.ceil(500.0 / once))), warm=1)
+
+    for mode in ("none", "mean"):
+        for nh in (0, 1):
+            T, J = nh + 1, C + U
+            with torch.no_grad():
+                win = torch.randn(B, T * C, H, W, device=dev) * 2 + 1
+                xz = torch.randn(B, T, U, H, W, device=dev)
+                static, bias = torch.randn(1, S, H, W, device=dev), torch.randn(1, C, H, W, device=dev)
+                yn = torch.randn(B, C, H, W, device=dev)
+                pre = ma.Preprocessor2D(img_shape=(H, W), n_history=nh, history_normalization_mode=mode, static_features=static,
+                                        bias_correction=bias).to(dev)
+                pre.train()
+                pre.cache_unpredicted_features(None, None, xz, None)
+                q = ma.GridQuadrature("naive", (H, W), normalize=True).to(dev).quad_weight
+                wts = torch.full((1, T, 1, 1, 1), 1.0 / T, device=dev)
+                stats = {}
+
+                def torch_assemble():
+                    xo = torch.cat([win.reshape(B, T, C, H, W), xz], dim=2)
+                    xf = xo.flatten(1, 2)
+                    if mode != "none":
+                        mean = torch.sum(torch.sum(xo * wts * q, dim=(-2, -1)), dim=1, keepdim=True).reshape(B, 1, J, 1, 1)
+                        std = torch.sqrt(torch.sum(torch.sum(torch.square(xo - mean) * wts * q, dim=(-2, -1)), dim=1, keepdim=True))
+                        stats["mean"], stats["std"] = mean.reshape(B, J, 1, 1), std.reshape(B, J, 1, 1)
+                        xf = (xf - torch.tile(stats["mean"], (1, T, 1, 1))) / torch.tile(stats["std"], (1, T, 1, 1))
+                    return torch.cat([xf, torch.tile(static, (B, 1, 1, 1))], dim=1)
+
+                def torch_finish():
+                    y = yn - bias
+                    return y * stats["std"][:, :C] + stats["mean"][:, :C] if mode != "none" else y
+
+                b_stats = (B * T * J + 1) * N * 4 if mode != "none" else 0
+                b_asm = (B * T * J + S + B * (T * J + S)) * N * 4
+                b_fin = (2 * B * C + C) * N * 4
+                err = (pre.assemble(win) - torch_assemble()).abs().max().item(), (pre.finish(yn) - torch_finish()).abs().max().item()
+                for rnd in range(3):
+                    ta, tta = timed(lambda: pre.assemble(win)), timed(torch_assemble)
+                    tf, ttf = timed(lambda: pre.finish(yn)), timed(torch_finish)
+                    print(f"preproc {mode:4s} n_history={nh} round {rnd}: assemble {ta:7.3f} ms {rate(b_stats + b_asm, ta)} "
+                          f"({(b_stats + b_asm) / 1e9:.2f} GB) | torch composition {tta:7.3f} ms = {tta / ta:5.2f} x | finish {tf:7.3f} ms "
+                          f"{rate(b_fin, tf)} ({b_fin / 1e9:.2f} GB) | torch composition {ttf:7.3f} ms = {ttf / tf:5.2f} x | "
+                          f"max |fused - torch| {err[0]:.1e} {err[1]:.1e}", flush=True)
+                if mode != "none":
+                    from makani_amd import preprocessor as pp
+                    src = pp._Src(win, xz, None, T)
+                    ts = timed(lambda: pp._stats(src, q, pre.history_time_weights))
+                    tasm = timed(lambda: pp._assemble(src, static[0], pre.history_mean.reshape(B, J), pre.history_std.reshape(B, J)))
+                    print(f"preproc {mode:4s} n_history={nh}: statistics {ts:7.3f} ms {rate(b_stats, ts)} ({b_stats / 1e9:.2f} GB) | assemble "
+                          f"launch {tasm:7.3f} ms {rate(b_asm, tasm)} ({b_asm / 1e9:.2f} GB)", flush=True)
+                del win, xz, static, bias, yn, pre
 
 
 if __name__ == "__main__":
