@@ -14,50 +14,12 @@
 // HBM-bound: forward 2 reads + 1 write of the tensor (the moments need the whole channel column before the first output;
 // C x VEC values do not fit a lane's registers at C = 384), backward 2 x (x, gy) reads + 1 write, wgrad 1 x (x, gy).
 // Moments: shifted sums (shift = the first channel's value) in fp32 — no cancellation for columns with a large mean.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
 constexpr int LNT = 256;
 constexpr int CU_ = 8;       // channel planes whose loads are issued together
-
-template <typename T, int VEC>
-__device__ __forceinline__ void ldpx(const T* p, float (&v)[VEC]);
-template <>
-__device__ __forceinline__ void ldpx<float, 4>(const float* p, float (&v)[4]) {
-    const f32x4 r = *reinterpret_cast<const f32x4*>(p);
-    v[0] = r[0], v[1] = r[1], v[2] = r[2], v[3] = r[3];
-}
-template <>
-__device__ __forceinline__ void ldpx<float, 1>(const float* p, float (&v)[1]) { v[0] = *p; }
-template <>
-__device__ __forceinline__ void ldpx<u16, 4>(const u16* p, float (&v)[4]) {
-    const uint2 r = *reinterpret_cast<const uint2*>(p);
-    v[0] = __uint_as_float(r.x << 16), v[1] = __uint_as_float(r.x & 0xffff0000u);
-    v[2] = __uint_as_float(r.y << 16), v[3] = __uint_as_float(r.y & 0xffff0000u);
-}
-template <>
-__device__ __forceinline__ void ldpx<u16, 1>(const u16* p, float (&v)[1]) { v[0] = bf16_to_f32(*p); }
-
-template <typename T, int VEC>
-__device__ __forceinline__ void stpx(T* p, const float (&v)[VEC]);
-template <>
-__device__ __forceinline__ void stpx<float, 4>(float* p, const float (&v)[4]) {
-    f32x4 r;
-    r[0] = v[0], r[1] = v[1], r[2] = v[2], r[3] = v[3];
-    *reinterpret_cast<f32x4*>(p) = r;
-}
-template <>
-__device__ __forceinline__ void stpx<float, 1>(float* p, const float (&v)[1]) { *p = v[0]; }
-template <>
-__device__ __forceinline__ void stpx<u16, 4>(u16* p, const float (&v)[4]) {
-    uint2 r;
-    r.x = pack_bf16x2(v[0], v[1]);
-    r.y = pack_bf16x2(v[2], v[3]);
-    *reinterpret_cast<uint2*>(p) = r;
-}
-template <>
-__device__ __forceinline__ void stpx<u16, 1>(u16* p, const float (&v)[1]) { *p = f32_to_bf16(v[0]); }
 
 // grid: (pixel tiles, B).  A lane owns VEC consecutive grid points of one sample.
 template <typename TI, typename TO, int VEC>
@@ -69,13 +31,13 @@ __global__ __launch_bounds__(LNT) void chan_ln_fwd_kernel(const TI* __restrict__
     const int b = blockIdx.y;
     const TI* xb = x + (long long)b * C * P + p0;
     float x0[VEC], s[VEC], q[VEC];
-    ldpx<TI, VEC>(xb, x0);
+    mk_ld<TI, VEC>(xb, x0);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) s[i] = 0.f, q[i] = 0.f;
     for (int c0 = 0; c0 < C; c0 += CU_) {
         float v[CU_][VEC];
 #pragma unroll
-        for (int u = 0; u < CU_; ++u) ldpx<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);      // all loads first
+        for (int u = 0; u < CU_; ++u) mk_ld<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);      // all loads first
 #pragma unroll
         for (int u = 0; u < CU_; ++u)
             if (c0 + u < C) {
@@ -95,13 +57,13 @@ __global__ __launch_bounds__(LNT) void chan_ln_fwd_kernel(const TI* __restrict__
         mean[i] = x0[i] + ms;
         rstd[i] = rsqrtf(fmaxf(q[i] * inv_c - ms * ms, 0.f) + eps);
     }
-    stpx<float, VEC>(stats + ((long long)b * 2 + 0) * P + p0, mean);
-    stpx<float, VEC>(stats + ((long long)b * 2 + 1) * P + p0, rstd);
+    mk_st<float, VEC>(stats + ((long long)b * 2 + 0) * P + p0, mean);
+    mk_st<float, VEC>(stats + ((long long)b * 2 + 1) * P + p0, rstd);
     TO* yb = y + (long long)b * C * P + p0;
     for (int c0 = 0; c0 < C; c0 += CU_) {
         float v[CU_][VEC];
 #pragma unroll
-        for (int u = 0; u < CU_; ++u) ldpx<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
+        for (int u = 0; u < CU_; ++u) mk_ld<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
 #pragma unroll
         for (int u = 0; u < CU_; ++u)
             if (c0 + u < C) {
@@ -109,7 +71,7 @@ __global__ __launch_bounds__(LNT) void chan_ln_fwd_kernel(const TI* __restrict__
                 float o[VEC];
 #pragma unroll
                 for (int i = 0; i < VEC; ++i) o[i] = fmaf((v[u][i] - mean[i]) * rstd[i], g, bt);
-                stpx<TO, VEC>(yb + (long long)(c0 + u) * P, o);
+                mk_st<TO, VEC>(yb + (long long)(c0 + u) * P, o);
             }
     }
 }
@@ -124,8 +86,8 @@ __global__ __launch_bounds__(LNT) void chan_ln_bwd_kernel(const TI* __restrict__
     const TI* xb = x + (long long)b * C * P + p0;
     const TG* gb = gy + (long long)b * C * P + p0;
     float mean[VEC], rstd[VEC], s1[VEC], s2[VEC];
-    ldpx<float, VEC>(stats + ((long long)b * 2 + 0) * P + p0, mean);
-    ldpx<float, VEC>(stats + ((long long)b * 2 + 1) * P + p0, rstd);
+    mk_ld<float, VEC>(stats + ((long long)b * 2 + 0) * P + p0, mean);
+    mk_ld<float, VEC>(stats + ((long long)b * 2 + 1) * P + p0, rstd);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) s1[i] = 0.f, s2[i] = 0.f;
     constexpr int U2 = CU_ / 2;
@@ -133,8 +95,8 @@ __global__ __launch_bounds__(LNT) void chan_ln_bwd_kernel(const TI* __restrict__
         float v[U2][VEC], g[U2][VEC];
 #pragma unroll
         for (int u = 0; u < U2; ++u) {
-            ldpx<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
-            ldpx<TG, VEC>(gb + (long long)min(c0 + u, C - 1) * P, g[u]);
+            mk_ld<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
+            mk_ld<TG, VEC>(gb + (long long)min(c0 + u, C - 1) * P, g[u]);
         }
 #pragma unroll
         for (int u = 0; u < U2; ++u)
@@ -156,8 +118,8 @@ __global__ __launch_bounds__(LNT) void chan_ln_bwd_kernel(const TI* __restrict__
         float v[U2][VEC], g[U2][VEC];
 #pragma unroll
         for (int u = 0; u < U2; ++u) {
-            ldpx<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
-            ldpx<TG, VEC>(gb + (long long)min(c0 + u, C - 1) * P, g[u]);
+            mk_ld<TI, VEC>(xb + (long long)min(c0 + u, C - 1) * P, v[u]);
+            mk_ld<TG, VEC>(gb + (long long)min(c0 + u, C - 1) * P, g[u]);
         }
 #pragma unroll
         for (int u = 0; u < U2; ++u)
@@ -169,7 +131,7 @@ __global__ __launch_bounds__(LNT) void chan_ln_bwd_kernel(const TI* __restrict__
                     const float xh = (v[u][i] - mean[i]) * rstd[i];
                     o[i] = rstd[i] * (gm * g[u][i] - s1[i] - xh * s2[i]);
                 }
-                stpx<TI, VEC>(ob + (long long)(c0 + u) * P, o);
+                mk_st<TI, VEC>(ob + (long long)(c0 + u) * P, o);
             }
     }
 }
@@ -190,8 +152,8 @@ __global__ __launch_bounds__(LNT) void chan_ln_wgrad_kernel(const TI* __restrict
         const float* mp = stats + (long long)b * 2 * P;
         for (long long p = a0 + threadIdx.x; p < a1; p += LNT) {
             float xv[1], gv[1];
-            ldpx<TI, 1>(xp + p, xv);
-            ldpx<TG, 1>(gp + p, gv);
+            mk_ld<TI, 1>(xp + p, xv);
+            mk_ld<TG, 1>(gp + p, gv);
             dg = fmaf(gv[0], (xv[0] - mp[p]) * mp[P + p], dg);
             db += gv[0];
         }

@@ -17,21 +17,12 @@
 // is the derivative of that loop with respect to the sorted members, scattered back through the ranks.
 // Ensemble sizes: every E in 2..32 — the kernels are instantiated for EM in {2, 4, 8, 16, 32} and run any E <= EM with the
 // surplus members predicated off.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
 constexpr int CNT = 256;
 constexpr int MAXE = 32;
-
-template <typename T>
-__device__ __forceinline__ float ldv(const T* p);
-template <>
-__device__ __forceinline__ float ldv<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ldv<u16>(const u16* p) { return bf16_to_f32(*p); }
-__device__ __forceinline__ void stv(float* p, float v) { *p = v; }
-__device__ __forceinline__ void stv(u16* p, float v) { *p = f32_to_bf16(v); }
 
 enum { CRPS_SKILLSPREAD = 0, CRPS_PWM = 1, CRPS_NAIVE = 2, CRPS_GAUSS = 3, CRPS_CDF = 4 };
 
@@ -198,27 +189,21 @@ __global__ __launch_bounds__(CNT) void crps_kernel(const TF* __restrict__ f, con
     for (long long p = (long long)blockIdx.x * CNT + threadIdx.x; p < hw; p += (long long)gridDim.x * CNT) {
         float v[EM];
 #pragma unroll
-        for (int e = 0; e < EM; ++e) v[e] = (e < E) ? ldv(fp + e * estride + p) : 0.f;
-        const float s = crps_point<EM, GRAD>(v, E, ldv(op + p), type, alpha, eps, ew);
+        for (int e = 0; e < EM; ++e) v[e] = (e < E) ? mk_ld(fp + e * estride + p) : 0.f;
+        const float s = crps_point<EM, GRAD>(v, E, mk_ld(op + p), type, alpha, eps, ew);
         const float wt = q[p] * (wp ? wp[p] : 1.f);
         if (GRAD) {
             TF* gp = gf + ((long long)b * E * C + c) * hw;
 #pragma unroll
             for (int e = 0; e < EM; ++e)
-                if (e < E) stv(gp + e * estride + p, go * wt * v[e]);
+                if (e < E) mk_st(gp + e * estride + p, go * wt * v[e]);
         } else {
             sum += wt * s;
         }
     }
     if (!GRAD) {
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float t = 0.f;
-            for (int i = 0; i < CNT / 64; ++i) t += red[i];
-            partial[(long long)plane * gridDim.x + blockIdx.x] = t;
-        }
+        const float t = mk_block_sum_t0<CNT>(sum, red);
+        if (threadIdx.x == 0) partial[(long long)plane * gridDim.x + blockIdx.x] = t;
     }
 }
 
@@ -293,39 +278,24 @@ __global__ __launch_bounds__(CNT) void crps_cplx_kernel(const float2* __restrict
         }
     }
     if (!GRAD) {
-        for (int o2 = 32; o2 > 0; o2 >>= 1) sum += __shfl_down(sum, o2, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float t = 0.f;
-            for (int i = 0; i < CNT / 64; ++i) t += red[i];
-            partial[(long long)plane * gridDim.x + blockIdx.x] = t;
-        }
+        const float t = mk_block_sum_t0<CNT>(sum, red);
+        if (threadIdx.x == 0) partial[(long long)plane * gridDim.x + blockIdx.x] = t;
     }
 }
 
 template <typename TF, typename TO, bool GRAD>
 int launch_e(int E, dim3 grid, hipStream_t s, const TF* f, const TO* obs, const float* q, const float* w, const float* gout,
              float* partial, TF* gf, int C, long long hw, int type, float alpha, float eps, const float* ew) {
-#define MK_CRPS_E(N)                                                                                                              \
-    if (E <= N) {                                                                                                                 \
-        hipLaunchKernelGGL((crps_kernel<TF, TO, N, GRAD>), grid, dim3(CNT), 0, s, f, obs, q, w, gout, partial, gf, E, C, hw, type, \
-                           alpha, eps, ew);                                                                                       \
-        return mk_check_launch("mk_crps");                                                                                        \
-    }
-    // the smallest instantiated capacity that holds E members
-    MK_CRPS_E(2) MK_CRPS_E(4) MK_CRPS_E(8) MK_CRPS_E(16) MK_CRPS_E(32)
-#undef MK_CRPS_E
-    mk_set_error("crps: ensemble size %d exceeds the register-resident limit of 32 members", E);
-    return MK_EUNSUP;
+    return mk_with_capacity(E, "crps", [&](auto em) {
+        hipLaunchKernelGGL((crps_kernel<TF, TO, em(), GRAD>), grid, dim3(CNT), 0, s, f, obs, q, w, gout, partial, gf, E, C, hw, type, alpha,
+                           eps, ew);
+        return mk_check_launch("mk_crps");
+    });
 }
 
 }  // namespace
 
-extern "C" int mk_crps_chunks(long long hw) {
-    long long c = (hw + 4 * CNT - 1) / (4 * CNT);
-    return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
-}
+extern "C" int mk_crps_chunks(long long hw) { return mk_plane_chunks(hw); }
 
 // grad == 0: partial (planes * mk_crps_chunks(hw)) f32 receives the chunk sums (the caller adds them up);
 // grad == 1: gf (same shape and dtype as f) receives gout[plane] * q * w * dcrps/df
@@ -337,8 +307,7 @@ extern "C" int mk_crps(const void* f, int f_dtype, const void* obs, int o_dtype,
     MK_REQUIRE(type >= 0 && type <= 4, "crps: unknown score type %d", type);
     MK_REQUIRE(!ens_w || type == CRPS_CDF, "crps: ensemble weights are defined for the cdf form only");
     MK_REQUIRE(grad ? (gout && gf) : (partial != nullptr), "crps: missing output");
-    MK_REQUIRE((long long)B * C <= 65535, "crps: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
-               (long long)B * C);
+    MK_REQUIRE_PLANES("crps", (long long)B * C);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)mk_crps_chunks(hw), (unsigned)(B * C));
 #define MK_CRPS_GO(TF, TO)                                                                                                          \
@@ -359,21 +328,16 @@ extern "C" int mk_crps_complex(const void* f, const void* obs, const float* q, c
                                void* gf, int B, int E, int C, long long hw, float alpha, int grad, void* stream) {
     MK_REQUIRE(f && obs && q && B > 0 && E >= 2 && E <= MAXE && C > 0 && hw > 0, "crps_complex: bad arguments (2 <= E <= 32)");
     MK_REQUIRE(grad ? (gout && gf) : (partial != nullptr), "crps_complex: missing output");
-    MK_REQUIRE((long long)B * C <= 65535, "crps_complex: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
-               (long long)B * C);
+    MK_REQUIRE_PLANES("crps_complex", (long long)B * C);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)mk_crps_chunks(hw), (unsigned)(B * C));
-#define MK_CX(N)                                                                                                                     \
-    if (E <= N) {                                                                                                                    \
-        if (grad)                                                                                                                    \
-            hipLaunchKernelGGL((crps_cplx_kernel<N, true>), grid, dim3(CNT), 0, s, (const float2*)f, (const float2*)obs, q, w, gout,  \
-                               partial, (float2*)gf, E, C, hw, alpha);                                                               \
-        else                                                                                                                         \
-            hipLaunchKernelGGL((crps_cplx_kernel<N, false>), grid, dim3(CNT), 0, s, (const float2*)f, (const float2*)obs, q, w, gout, \
-                               partial, (float2*)gf, E, C, hw, alpha);                                                               \
-        return mk_check_launch("mk_crps_complex");                                                                                   \
-    }
-    MK_CX(2) MK_CX(4) MK_CX(8) MK_CX(16) MK_CX(32)
-#undef MK_CX
-    return MK_EUNSUP;
+    return mk_with_capacity(E, "crps_complex", [&](auto em) {
+        if (grad)
+            hipLaunchKernelGGL((crps_cplx_kernel<em(), true>), grid, dim3(CNT), 0, s, (const float2*)f, (const float2*)obs, q, w, gout, partial,
+                               (float2*)gf, E, C, hw, alpha);
+        else
+            hipLaunchKernelGGL((crps_cplx_kernel<em(), false>), grid, dim3(CNT), 0, s, (const float2*)f, (const float2*)obs, q, w, gout, partial,
+                               (float2*)gf, E, C, hw, alpha);
+        return mk_check_launch("mk_crps_complex");
+    });
 }

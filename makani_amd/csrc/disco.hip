@@ -17,18 +17,9 @@
 // 3.5 GB of traffic); a first version that walked the lists with dependent scalar loads per entry ran 10 x slower.
 // Adjoint: on equal longitude counts the same correlation over transposed lists (gradient rows of one basis function at a
 // time in LDS); otherwise a deterministic gather per input point.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
-
-template <typename T>
-__device__ __forceinline__ float ldf(const T* p);
-template <>
-__device__ __forceinline__ float ldf<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float ldf<u16>(const u16* p) { return bf16_to_f32(*p); }
-__device__ __forceinline__ void stf(float* p, float v) { *p = v; }
-__device__ __forceinline__ void stf(u16* p, float v) { *p = f32_to_bf16(v); }
 
 constexpr int DNT = 256;
 constexpr int DCH = 512;          // list entries staged in LDS per chunk
@@ -102,7 +93,7 @@ __device__ __forceinline__ void stage_rows(float* xs, const T* __restrict__ src0
                                            int nelem, int tid) {
     for (int b = 0; b < PB; ++b) {
         const T* src = src0 + (long long)min(first + b, planes - 1) * plane_step;
-        for (int e = tid; e < nelem; e += DNT) xs[e * PB + b] = ldf(src + e);
+        for (int e = tid; e < nelem; e += DNT) xs[e * PB + b] = mk_ld(src + e);
     }
 }
 
@@ -145,7 +136,7 @@ __global__ __launch_bounds__(DNT) void disco_fwd_kernel(const T* __restrict__ x,
             if (p < nlon_out) {
 #pragma unroll
                 for (int b = 0; b < PB; ++b)
-                    if (b < npl) stf(y + ((p0 + b) * (long long)K + k) * plane_out + (long long)t * nlon_out + p, acc[q][b]);
+                    if (b < npl) mk_st(y + ((p0 + b) * (long long)K + k) * plane_out + (long long)t * nlon_out + p, acc[q][b]);
             }
         }
     }
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(DNT) void disco_bwd_same_kernel(const T* __restrict
         if (p < nlon) {
 #pragma unroll
             for (int b = 0; b < PB; ++b)
-                if (b < npl) stf(gx + ((long long)(p0 + b) * nlat_in + i) * nlon + p, acc[q][b]);
+                if (b < npl) mk_st(gx + ((long long)(p0 + b) * nlat_in + i) * nlon + p, acc[q][b]);
         }
     }
 }
@@ -217,24 +208,13 @@ __global__ __launch_bounds__(DNT) void disco_bwd_kernel(const T* __restrict__ gy
             int d = q - nlon[n];
             d += (d < 0) ? nlon_in : 0;
             const int p = d / s;
-            if (p * s == d) acc = fmaf(nval[n], ldf(g + nk[n] * plane_out + (long long)nt[n] * nlon_out + p), acc);
+            if (p * s == d) acc = fmaf(nval[n], mk_ld(g + nk[n] * plane_out + (long long)nt[n] * nlon_out + p), acc);
         }
-        stf(gx + ((long long)pl * nlat_in + i) * nlon_in + q, acc);
+        mk_st(gx + ((long long)pl * nlat_in + i) * nlon_in + q, acc);
     }
 }
 
 // ---- bilinear resampling --------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    float tot = 0.f;
-    for (int q = 0; q < DNT / 64; ++q) tot += red[q];
-    return tot;
-}
-
 // row source: r >= 0 input row r; -1 / -2: the mean over longitude of the first / last input row (pole extension)
 template <typename T>
 __global__ __launch_bounds__(DNT) void resample_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, const int* __restrict__ lat_a,
@@ -251,23 +231,23 @@ __global__ __launch_bounds__(DNT) void resample_fwd_kernel(const T* __restrict__
     if (a < 0) {
         const T* row = xp + (long long)(a == -1 ? 0 : nlat_in - 1) * nlon_in;
         float sacc = 0.f;
-        for (int j = tid; j < nlon_in; j += DNT) sacc += ldf(row + j);
-        ma = block_sum(sacc, red) / (float)nlon_in;
+        for (int j = tid; j < nlon_in; j += DNT) sacc += mk_ld(row + j);
+        ma = mk_block_sum_all<DNT>(sacc, red) / (float)nlon_in;
     }
     if (b < 0) {
         const T* row = xp + (long long)(b == -1 ? 0 : nlat_in - 1) * nlon_in;
         float sacc = 0.f;
-        for (int j = tid; j < nlon_in; j += DNT) sacc += ldf(row + j);
-        mb = block_sum(sacc, red) / (float)nlon_in;
+        for (int j = tid; j < nlon_in; j += DNT) sacc += mk_ld(row + j);
+        mb = mk_block_sum_all<DNT>(sacc, red) / (float)nlon_in;
     }
     const T* ra = xp + (long long)max(a, 0) * nlon_in;
     const T* rb = xp + (long long)max(b, 0) * nlon_in;
     for (int p = tid; p < nlon_out; p += DNT) {
         const int l = lon_l[p], r = lon_r[p];
-        const float al = a < 0 ? ma : ldf(ra + l), ar = a < 0 ? ma : ldf(ra + r);
-        const float bl = b < 0 ? mb : ldf(rb + l), br = b < 0 ? mb : ldf(rb + r);
+        const float al = a < 0 ? ma : mk_ld(ra + l), ar = a < 0 ? ma : mk_ld(ra + r);
+        const float bl = b < 0 ? mb : mk_ld(rb + l), br = b < 0 ? mb : mk_ld(rb + r);
         const float yl = al + w * (bl - al), yr = ar + w * (br - ar);           // latitude first, as the reference
-        stf(y + ((long long)pl * nlat_out + t) * nlon_out + p, yl + lon_w[p] * (yr - yl));
+        mk_st(y + ((long long)pl * nlat_out + t) * nlon_out + p, yl + lon_w[p] * (yr - yl));
     }
 }
 
@@ -296,7 +276,7 @@ __global__ __launch_bounds__(DNT) void resample_bwd_kernel(const T* __restrict__
         const T* row = g + (long long)t * nlon_out;
         float sacc = 0.f;
         for (int p = tid; p < nlon_out; p += DNT) {
-            const float v = ldf(row + p);
+            const float v = mk_ld(row + p);
             rowbuf[p] = v;
             sacc += v;
         }
@@ -308,8 +288,8 @@ __global__ __launch_bounds__(DNT) void resample_bwd_kernel(const T* __restrict__
         for (int n = pole_off[which]; n < pole_off[which + 1]; ++n) {
             float sacc = 0.f;
             const T* row = g + (long long)pole_t[n] * nlon_out;
-            for (int p = tid; p < nlon_out; p += DNT) sacc += ldf(row + p);
-            pole += pole_wt[n] * block_sum(sacc, red);
+            for (int p = tid; p < nlon_out; p += DNT) sacc += mk_ld(row + p);
+            pole += pole_wt[n] * mk_block_sum_all<DNT>(sacc, red);
         }
         pole /= (float)nlon_in;
     }
@@ -332,7 +312,7 @@ __global__ __launch_bounds__(DNT) void resample_bwd_kernel(const T* __restrict__
 #pragma unroll
     for (int q = 0; q < MAXQ; ++q) {
         const int j = tid + q * DNT;
-        if (j < nlon_in) stf(gx + ((long long)pl * nlat_in + i) * nlon_in + j, acc[q] + pole);
+        if (j < nlon_in) mk_st(gx + ((long long)pl * nlat_in + i) * nlon_in + j, acc[q] + pole);
     }
 }
 

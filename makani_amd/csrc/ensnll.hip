@@ -16,21 +16,12 @@
 // No NaN masks: the reference has none.  E = 1: the variance is 0, the clamp is active everywhere.
 // Sums are deterministic: every block writes the sum of its chunk (wave shuffles, then the four waves in order), the caller
 // adds the chunks of a plane in order.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
 constexpr int NNT = 256;
 constexpr int NMAXE = 32;
-
-template <typename T>
-__device__ __forceinline__ float nll_ld(const T* p);
-template <>
-__device__ __forceinline__ float nll_ld<float>(const float* p) { return *p; }
-template <>
-__device__ __forceinline__ float nll_ld<u16>(const u16* p) { return bf16_to_f32(*p); }
-__device__ __forceinline__ void nll_st(float* p, float v) { *p = v; }
-__device__ __forceinline__ void nll_st(u16* p, float v) { *p = f32_to_bf16(v); }
 
 // grid: (chunks, planes = B * C).  EM: compiled capacity, members e >= E are predicated off.
 template <typename TF, int EM, bool GRAD>
@@ -50,7 +41,7 @@ __global__ __launch_bounds__(NNT) void ens_nll_kernel(const TF* __restrict__ f, 
     for (long long p = (long long)blockIdx.x * NNT + threadIdx.x; p < hw; p += (long long)gridDim.x * NNT) {
         float d[EM];
 #pragma unroll
-        for (int e = 0; e < EM; ++e) d[e] = (e < E) ? nll_ld(fp + e * estride + p) : 0.f;
+        for (int e = 0; e < EM; ++e) d[e] = (e < E) ? mk_ld(fp + e * estride + p) : 0.f;
         const float piv = d[0];
         float md = 0.f;                // mu - piv
 #pragma unroll
@@ -76,51 +67,35 @@ __global__ __launch_bounds__(NNT) void ens_nll_kernel(const TF* __restrict__ f, 
             TF* gp = gf + foff;
 #pragma unroll
             for (int e = 0; e < EM; ++e)
-                if (e < E) nll_st(gp + e * estride + p, sc * (dmu + 2.f * ds2 * d[e]));
+                if (e < E) mk_st(gp + e * estride + p, sc * (dmu + 2.f * ds2 * d[e]));
         } else {
             sum += wt * 0.5f * (logf(s2) + r * r * inv);
         }
     }
     if (!GRAD) {
-        for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float t = 0.f;
-            for (int i = 0; i < NNT / 64; ++i) t += red[i];
-            partial[(long long)plane * gridDim.x + blockIdx.x] = t;
-        }
+        const float t = mk_block_sum_t0<NNT>(sum, red);
+        if (threadIdx.x == 0) partial[(long long)plane * gridDim.x + blockIdx.x] = t;
     }
 }
 
 template <typename TF, bool GRAD>
 int nll_launch(int E, dim3 grid, hipStream_t s, const TF* f, const float* obs, const float* q, const float* w, const float* gout, float* partial,
                TF* gf, int C, long long hw, float eps2) {
-#define MK_NLL_E(N)                                                                                                                        \
-    if (E <= N) {                                                                                                                          \
-        hipLaunchKernelGGL((ens_nll_kernel<TF, N, GRAD>), grid, dim3(NNT), 0, s, f, obs, q, w, gout, partial, gf, E, C, hw, eps2);        \
-        return mk_check_launch("mk_ens_nll");                                                                                              \
-    }
-    // the smallest instantiated capacity that holds E members
-    MK_NLL_E(2) MK_NLL_E(4) MK_NLL_E(8) MK_NLL_E(16) MK_NLL_E(32)
-#undef MK_NLL_E
-    mk_set_error("ens_nll: ensemble size %d exceeds the register-resident limit of 32 members", E);
-    return MK_EUNSUP;
+    return mk_with_capacity(E, "ens_nll", [&](auto em) {
+        hipLaunchKernelGGL((ens_nll_kernel<TF, em(), GRAD>), grid, dim3(NNT), 0, s, f, obs, q, w, gout, partial, gf, E, C, hw, eps2);
+        return mk_check_launch("mk_ens_nll");
+    });
 }
 
 }  // namespace
 
-extern "C" int mk_ens_nll_chunks(long long hw) {
-    long long c = (hw + 4 * NNT - 1) / (4 * NNT);
-    return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
-}
+extern "C" int mk_ens_nll_chunks(long long hw) { return mk_plane_chunks(hw); }
 
 extern "C" int mk_ens_nll(const void* f, int f_dtype, const float* obs, const float* q, const float* w, const float* gout, float* partial,
                           void* gf, int B, int E, int C, long long hw, float eps, int grad, void* stream) {
     MK_REQUIRE(f && obs && q && B > 0 && E >= 1 && E <= NMAXE && C > 0 && hw > 0, "ens_nll: bad arguments (1 <= E <= 32)");
     MK_REQUIRE(grad ? (gout && gf) : (partial != nullptr), "ens_nll: missing output");
-    MK_REQUIRE((long long)B * C <= 65535, "ens_nll: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
-               (long long)B * C);
+    MK_REQUIRE_PLANES("ens_nll", (long long)B * C);
     MK_REQUIRE(f_dtype == MK_F32 || f_dtype == MK_BF16, "ens_nll: members are f32 or bf16");
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)mk_ens_nll_chunks(hw), (unsigned)(B * C));

@@ -35,7 +35,7 @@
 // Stage 3, mk_escore_grad: gf[b][e][c][n] = gout[b][co] * wt * sum_k table[b][co][s][k] * d term_k / d f_e in the members'
 //   dtype; complex gradients in torch's convention (d |z|^2 = 2 z).  One block owns a tile of 8 members of its points and
 //   walks all tiles for the partners: E <= 8 reads everything once, larger ensembles re-read T times.  Masked points get 0.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
@@ -53,15 +53,15 @@ template <>
 struct Val<float> {
     typedef float V;       // value in registers
     typedef float O;       // observation in memory
-    static __device__ __forceinline__ V ld(const float* p) { return *p; }
-    static __device__ __forceinline__ void st(float* p, V v) { *p = v; }
+    static __device__ __forceinline__ V ld(const float* p) { return mk_ld(p); }
+    static __device__ __forceinline__ void st(float* p, V v) { mk_st(p, v); }
 };
 template <>
 struct Val<u16> {
     typedef float V;
     typedef float O;
-    static __device__ __forceinline__ V ld(const u16* p) { return bf16_to_f32(*p); }
-    static __device__ __forceinline__ void st(u16* p, V v) { *p = f32_to_bf16(v); }
+    static __device__ __forceinline__ V ld(const u16* p) { return mk_ld(p); }
+    static __device__ __forceinline__ void st(u16* p, V v) { mk_st(p, v); }
 };
 template <>
 struct Val<float2> {
@@ -404,34 +404,26 @@ __global__ __launch_bounds__(ENT) void escore_grad_kernel(const T* __restrict__ 
     }
 }
 
-int chunks_of(long long seglen) {
-    long long c = (seglen + 4 * ENT - 1) / (4 * ENT);
-    return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
-}
-
 // the smallest instantiated tile that holds E members; more than one tile: always tiles of 8
 int tile_of(int E) { return E <= 2 ? 2 : (E <= 4 ? 4 : ETILE); }
 
 template <typename T, int PM>
 int launch_sums(const T* f, const typename Val<T>::O* obs, const float* q, const float* w, float* out, int E, int C, long long seglen,
                 int nanmode, float p, dim3 grid, int ntile, hipStream_t s) {
-    switch (tile_of(E)) {
-        case 2: hipLaunchKernelGGL((escore_sums_kernel<T, PM, 2>), grid, dim3(ENT), 0, s, f, obs, q, w, out, E, C, seglen, ntile, nanmode, p); break;
-        case 4: hipLaunchKernelGGL((escore_sums_kernel<T, PM, 4>), grid, dim3(ENT), 0, s, f, obs, q, w, out, E, C, seglen, ntile, nanmode, p); break;
-        default: hipLaunchKernelGGL((escore_sums_kernel<T, PM, ETILE>), grid, dim3(ENT), 0, s, f, obs, q, w, out, E, C, seglen, ntile, nanmode, p);
-    }
-    return mk_check_launch("mk_escore_sums");
+    return mk_with_capacity<ETILE>(tile_of(E), "escore_sums", [&](auto em) {
+        hipLaunchKernelGGL((escore_sums_kernel<T, PM, em()>), grid, dim3(ENT), 0, s, f, obs, q, w, out, E, C, seglen, ntile, nanmode, p);
+        return mk_check_launch("mk_escore_sums");
+    });
 }
 
 template <typename T, int PM>
 int launch_grad(const T* f, const typename Val<T>::O* obs, const float* q, const float* w, const float* table, const float* gout, T* gf,
                 int E, int C, int Cout, long long seglen, int nanmode, float p, dim3 grid, int ntile, hipStream_t s) {
-    switch (tile_of(E)) {
-        case 2: hipLaunchKernelGGL((escore_grad_kernel<T, PM, 2>), grid, dim3(ENT), 0, s, f, obs, q, w, table, gout, gf, E, C, Cout, seglen, ntile, nanmode, p); break;
-        case 4: hipLaunchKernelGGL((escore_grad_kernel<T, PM, 4>), grid, dim3(ENT), 0, s, f, obs, q, w, table, gout, gf, E, C, Cout, seglen, ntile, nanmode, p); break;
-        default: hipLaunchKernelGGL((escore_grad_kernel<T, PM, ETILE>), grid, dim3(ENT), 0, s, f, obs, q, w, table, gout, gf, E, C, Cout, seglen, ntile, nanmode, p);
-    }
-    return mk_check_launch("mk_escore_grad");
+    return mk_with_capacity<ETILE>(tile_of(E), "escore_grad", [&](auto em) {
+        hipLaunchKernelGGL((escore_grad_kernel<T, PM, em()>), grid, dim3(ENT), 0, s, f, obs, q, w, table, gout, gf, E, C, Cout, seglen, ntile,
+                           nanmode, p);
+        return mk_check_launch("mk_escore_grad");
+    });
 }
 
 int pmode_of(float p) { return p == 2.f ? P_TWO : (p == 1.f ? P_ONE : P_ANY); }
@@ -445,7 +437,7 @@ bool common_args_ok(int kind, int B, int E, int C, long long N, int S, float p) 
 
 extern "C" long long mk_escore_sums_workspace(int B, int E, int C, long long N, int S, int nanmode) {
     if (B <= 0 || E <= 0 || C <= 0 || N <= 0 || S <= 0) return 0;
-    const int chunks = chunks_of(N / S);
+    const int chunks = mk_plane_chunks(N / S);
     const long long K = E + (long long)E * (E - 1) / 2;
     long long ws = chunks > 1 ? (long long)B * C * S * chunks * K : 0;
     if (nanmode == 1 && E > ETILE) ws += (long long)B * C * N;
@@ -458,7 +450,7 @@ extern "C" int mk_escore_sums(const void* f, int kind, const void* obs, const fl
                "escore_sums: bad arguments (1 <= E <= 32, p >= 1, complex members p = 2, N a multiple of S)");
     MK_REQUIRE(nanmode == 0 || nanmode == 1, "escore_sums: unknown NaN mode %d", nanmode);
     const long long seglen = N / S;
-    const int chunks = chunks_of(seglen), EM = tile_of(E), ntile = (E + EM - 1) / EM, npairs = ntile * (ntile + 1) / 2;
+    const int chunks = mk_plane_chunks(seglen), EM = tile_of(E), ntile = (E + EM - 1) / EM, npairs = ntile * (ntile + 1) / 2;
     const int K = E + E * (E - 1) / 2;
     MK_REQUIRE((long long)B * C * npairs <= 65535, "escore_sums: too many planes");
     MK_REQUIRE(ws || mk_escore_sums_workspace(B, E, C, N, S, nanmode) == 0, "escore_sums: missing workspace");
@@ -466,7 +458,7 @@ extern "C" int mk_escore_sums(const void* f, int kind, const void* obs, const fl
     float* partial = chunks > 1 ? ws : sums;
     float* wm = chunks > 1 ? ws + (long long)B * C * S * chunks * K : ws;
     const dim3 grid((unsigned)chunks, (unsigned)S, (unsigned)(B * C * npairs));
-    const dim3 mgrid((unsigned)chunks_of(N), (unsigned)(B * C));
+    const dim3 mgrid((unsigned)mk_plane_chunks(N), (unsigned)(B * C));
     const bool premask = nanmode == 1 && ntile > 1;
     int rc;
 #define MK_ES_MASK(T)                                                                                                                 \
@@ -529,7 +521,7 @@ extern "C" int mk_escore_grad(const void* f, int kind, const void* obs, const fl
     const int EM = tile_of(E), ntile = (E + EM - 1) / EM;
     MK_REQUIRE((long long)B * C * ntile <= 65535, "escore_grad: too many planes");
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)chunks_of(seglen), (unsigned)S, (unsigned)(B * C * ntile));
+    const dim3 grid((unsigned)mk_plane_chunks(seglen), (unsigned)S, (unsigned)(B * C * ntile));
     if (kind == 2)
         return launch_grad<float2, P_TWO>((const float2*)f, (const float2*)obs, q, w, table, gout, (float2*)gf, E, C, Cout, seglen, nanmode, p, grid,
                                           ntile, s);

@@ -22,43 +22,13 @@
 // plane in chunk order.  The arithmetic of one sum does not depend on which other sums are selected (`which` is a run-time,
 // block-uniform value and every accumulation is an explicit fmaf), so all-at-once equals one-at-a-time bit for bit.
 // 16-byte path (P = 4): N a multiple of 4 and every pointer 16-byte aligned; otherwise one point per thread (P = 1).
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
 constexpr int MNT = 256;
 constexpr int MMAXE = 32;
 constexpr int MDET = 5;              // sums of mk_metric_det_sums
-
-template <typename T, int P>
-__device__ __forceinline__ void m_ld(const T* p, float (&v)[P]);
-template <>
-__device__ __forceinline__ void m_ld<float, 1>(const float* p, float (&v)[1]) { v[0] = *p; }
-template <>
-__device__ __forceinline__ void m_ld<u16, 1>(const u16* p, float (&v)[1]) { v[0] = bf16_to_f32(*p); }
-template <>
-__device__ __forceinline__ void m_ld<float, 4>(const float* p, float (&v)[4]) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-    v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
-}
-template <>
-__device__ __forceinline__ void m_ld<u16, 4>(const u16* p, float (&v)[4]) {
-    const s16x4 t = *reinterpret_cast<const s16x4*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = bf16_to_f32((u16)t[j]);
-}
-
-// the block's sum of one per-thread value: wave shuffles, then the four waves in order (red: MNT / 64 floats)
-__device__ __forceinline__ void m_block_sum(float v, float* red, float* dst) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float t = 0.f;
-        for (int i = 0; i < MNT / 64; ++i) t += red[i];
-        *dst = t;
-    }
-}
 
 // grid: (chunks, planes = B * C).  partial[(plane * chunks + chunk) * 5 + k]
 template <typename TX, typename TY, int P>
@@ -74,11 +44,11 @@ __global__ __launch_bounds__(MNT) void metric_det_kernel(const TX* __restrict__ 
     float s[MDET] = {0.f, 0.f, 0.f, 0.f, 0.f};
     for (long long i = ((long long)blockIdx.x * MNT + threadIdx.x) * P; i < n; i += (long long)gridDim.x * MNT * P) {
         float xv[P], yv[P], qv[P], wv[P], bv[P];
-        m_ld<TX, P>(xp + i, xv);
-        m_ld<TY, P>(yp + i, yv);
-        m_ld<float, P>(q + i, qv);
-        if (wp) m_ld<float, P>(wp + i, wv);
-        if (bp) m_ld<float, P>(bp + i, bv);
+        mk_ld<TX, P>(xp + i, xv);
+        mk_ld<TY, P>(yp + i, yv);
+        mk_ld<float, P>(q + i, qv);
+        if (wp) mk_ld<float, P>(wp + i, wv);
+        if (bp) mk_ld<float, P>(bp + i, bv);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             const float wt = wp ? qv[j] * wv[j] : qv[j];
@@ -95,7 +65,10 @@ __global__ __launch_bounds__(MNT) void metric_det_kernel(const TX* __restrict__ 
     float* dst = partial + ((long long)plane * gridDim.x + blockIdx.x) * MDET;
 #pragma unroll
     for (int k = 0; k < MDET; ++k)
-        if (which & (1 << k)) m_block_sum(s[k], red[k], dst + k);          // (which is uniform: every thread reaches the barrier)
+        if (which & (1 << k)) {          // (which is uniform: every thread reaches the barrier)
+            const float t = mk_block_sum_t0<MNT>(s[k], red[k]);
+            if (threadIdx.x == 0) dst[k] = t;
+        }
 }
 
 // grid: (chunks, planes = B * C).  EM: compiled capacity, members e >= E are predicated off.
@@ -125,15 +98,15 @@ __global__ __launch_bounds__(MNT) void metric_ens_kernel(const TF* __restrict__ 
 #pragma unroll
         for (int e = 0; e < EM; ++e) {
             if (e < E) {
-                m_ld<TF, P>(fp + e * estride + i, d[e]);
+                mk_ld<TF, P>(fp + e * estride + i, d[e]);
             } else {
 #pragma unroll
                 for (int j = 0; j < P; ++j) d[e][j] = 0.f;
             }
         }
-        m_ld<float, P>(op + i, ov);
-        m_ld<float, P>(q + i, qv);
-        if (wp) m_ld<float, P>(wp + i, wv);
+        mk_ld<float, P>(op + i, ov);
+        mk_ld<float, P>(q + i, qv);
+        if (wp) mk_ld<float, P>(wp + i, wv);
 #pragma unroll
         for (int j = 0; j < P; ++j) {
             const float wt = wp ? qv[j] * wv[j] : qv[j];
@@ -165,8 +138,14 @@ __global__ __launch_bounds__(MNT) void metric_ens_kernel(const TF* __restrict__ 
     }
     const int K = E + 3;
     float* dst = partial + ((long long)plane * gridDim.x + blockIdx.x) * K;
-    if (which & 1) m_block_sum(skill, red[0], dst);
-    if (which & 2) m_block_sum(spread, red[1], dst + 1);
+    if (which & 1) {
+        const float t = mk_block_sum_t0<MNT>(skill, red[0]);
+        if (tid == 0) dst[0] = t;
+    }
+    if (which & 2) {
+        const float t = mk_block_sum_t0<MNT>(spread, red[1]);
+        if (tid == 0) dst[1] = t;
+    }
     if (hist) {
         __syncthreads();
         const int lane = tid & 63;
@@ -199,8 +178,6 @@ int finish(const float* ws, float* out, long long planes, int chunks, int K, int
     return mk_check_launch(what);
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 template <typename TX, typename TY>
 int det_launch(bool vec, dim3 grid, hipStream_t s, const void* x, const void* y, const float* bias, const float* w, const float* q, float* ws,
                int C, long long n, int which) {
@@ -214,41 +191,32 @@ int det_launch(bool vec, dim3 grid, hipStream_t s, const void* x, const void* y,
 template <typename TF>
 int ens_launch(bool vec, dim3 grid, hipStream_t s, const TF* f, const float* obs, const float* w, const float* q, float* ws, int E, int C,
                long long n, int which) {
-#define MK_MET_E(N, PV)                                                                                                               \
-    if (E <= N) {                                                                                                                     \
-        if (vec && PV == 4)                                                                                                           \
-            hipLaunchKernelGGL((metric_ens_kernel<TF, N, PV>), grid, dim3(MNT), 0, s, f, obs, w, q, ws, E, C, n, which);              \
-        else                                                                                                                          \
-            hipLaunchKernelGGL((metric_ens_kernel<TF, N, 1>), grid, dim3(MNT), 0, s, f, obs, w, q, ws, E, C, n, which);               \
-        return mk_check_launch("mk_metric_ens_sums");                                                                                 \
-    }
-    // the smallest instantiated capacity that holds E members; 32 members x 4 points would be 128 registers of members alone: one point
-    MK_MET_E(2, 4) MK_MET_E(4, 4) MK_MET_E(8, 4) MK_MET_E(16, 4) MK_MET_E(32, 1)
-#undef MK_MET_E
-    mk_set_error("metric_ens_sums: ensemble size %d exceeds the register-resident limit of 32 members", E);
-    return MK_EUNSUP;
+    return mk_with_capacity(E, "metric_ens_sums", [&](auto em) {
+        constexpr int PV = em() < 32 ? 4 : 1;          // 32 members x 4 points would be 128 registers of members alone: one point
+        if (vec && PV == 4)
+            hipLaunchKernelGGL((metric_ens_kernel<TF, em(), PV>), grid, dim3(MNT), 0, s, f, obs, w, q, ws, E, C, n, which);
+        else
+            hipLaunchKernelGGL((metric_ens_kernel<TF, em(), 1>), grid, dim3(MNT), 0, s, f, obs, w, q, ws, E, C, n, which);
+        return mk_check_launch("mk_metric_ens_sums");
+    });
 }
 
 }  // namespace
 
-extern "C" int mk_metric_chunks(long long n) {
-    long long c = (n + 4 * MNT - 1) / (4 * MNT);
-    return (int)(c < 1 ? 1 : (c > 64 ? 64 : c));
-}
+extern "C" int mk_metric_chunks(long long n) { return mk_plane_chunks(n); }
 
 extern "C" int mk_metric_det_sums(const void* x, int x_dtype, const void* y, int y_dtype, const float* bias, const float* w, const float* q,
                                   float* out, float* ws, int B, int C, long long n, int which, void* stream) {
     MK_REQUIRE(x && y && q && out && ws, "metric_det_sums: null pointer (x, y, q, out and ws are required)");
     MK_REQUIRE(B > 0 && C > 0, "metric_det_sums: B = %d, C = %d must be positive", B, C);
     MK_REQUIRE(n > 0, "metric_det_sums: N = %lld points per plane must be positive", n);
-    MK_REQUIRE((long long)B * C <= 65535, "metric_det_sums: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
-               (long long)B * C);
+    MK_REQUIRE_PLANES("metric_det_sums", (long long)B * C);
     MK_REQUIRE((x_dtype == MK_F32 || x_dtype == MK_BF16) && (y_dtype == MK_F32 || y_dtype == MK_BF16), "metric_det_sums: x and y are f32 or bf16");
     MK_REQUIRE(which > 0 && which < 32, "metric_det_sums: which = %d selects no sum or an unknown one (bits 0..4)", which);
     hipStream_t s = (hipStream_t)stream;
     const int chunks = mk_metric_chunks(n);
     const dim3 grid((unsigned)chunks, (unsigned)(B * C));
-    const bool vec = n % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(q) && aligned16(w) && aligned16(bias);
+    const bool vec = n % 4 == 0 && mk_aligned16(x) && mk_aligned16(y) && mk_aligned16(q) && mk_aligned16(w) && mk_aligned16(bias);
     int rc;
     if (x_dtype == MK_F32)
         rc = y_dtype == MK_F32 ? det_launch<float, float>(vec, grid, s, x, y, bias, w, q, ws, C, n, which)
@@ -266,14 +234,13 @@ extern "C" int mk_metric_ens_sums(const void* f, int f_dtype, const float* obs, 
     MK_REQUIRE(E >= 1 && E <= MMAXE, "metric_ens_sums: ensemble size %d outside 1 <= E <= 32", E);
     MK_REQUIRE(B > 0 && C > 0, "metric_ens_sums: B = %d, C = %d must be positive", B, C);
     MK_REQUIRE(n > 0, "metric_ens_sums: N = %lld points per plane must be positive", n);
-    MK_REQUIRE((long long)B * C <= 65535, "metric_ens_sums: %lld planes (B * C) exceed the plane limit of 65535 (one grid row per plane)",
-               (long long)B * C);
+    MK_REQUIRE_PLANES("metric_ens_sums", (long long)B * C);
     MK_REQUIRE(f_dtype == MK_F32 || f_dtype == MK_BF16, "metric_ens_sums: members are f32 or bf16");
     MK_REQUIRE(which > 0 && which < 8, "metric_ens_sums: which = %d selects no sum or an unknown one (bits 0..2)", which);
     hipStream_t s = (hipStream_t)stream;
     const int chunks = mk_metric_chunks(n);
     const dim3 grid((unsigned)chunks, (unsigned)(B * C));
-    const bool vec = n % 4 == 0 && aligned16(f) && aligned16(obs) && aligned16(q) && aligned16(w);
+    const bool vec = n % 4 == 0 && mk_aligned16(f) && mk_aligned16(obs) && mk_aligned16(q) && mk_aligned16(w);
     const int rc = f_dtype == MK_F32 ? ens_launch<float>(vec, grid, s, (const float*)f, obs, w, q, ws, E, C, n, which)
                                      : ens_launch<u16>(vec, grid, s, (const u16*)f, obs, w, q, ws, E, C, n, which);
     if (rc) return rc;

@@ -2,7 +2,7 @@
 // interleaved real view).  One HBM pass: reads p, g, m, v and writes p, m, v (28 B / element);
 // the global-norm clipping coefficient is read from device memory so the host never syncs.
 // Update rule = torch.optim.AdamW (decoupled weight decay, bias-corrected moments).
-#include "common.h"
+#include "block_io.h"
 
 // The step streams 28 bytes per element through the chip exactly once (16 GB per step for the SFNO's spectral weights)
 // and nothing of it is read again before the caches have turned over many times: non-temporal loads and stores, and a grid
@@ -154,15 +154,8 @@ __global__ __launch_bounds__(NT) void sumsq_multi_kernel(const SumsqMulti a, flo
     } else {
         for (long long i = e0 + threadIdx.x; i < e1; i += NT) s += g[i] * g[i];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tsum = 0.f;
-        for (int i = 0; i < NT / 64; ++i) tsum += red[i];
-        partial[blockIdx.x] = tsum;
-    }
+    const float tsum = mk_block_sum_t0<NT>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tsum;
 }
 
 // out[0] = clip coefficient min(1, max_norm / (norm + 1e-6)), out[1] = norm   (fixed summation order)
@@ -247,15 +240,8 @@ static __global__ __launch_bounds__(NT) void gather_partials_kernel(const SumsqM
     while (t + 1 < a.count && (int)blockIdx.x >= a.first[t + 1]) ++t;
     const long long i = (long long)((int)blockIdx.x - a.first[t]) * NT + threadIdx.x;
     float s = i < a.n[t] ? a.g[t][i] : 0.f;                 // NT of the producer's partials -> one (fixed order)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float tsum = 0.f;
-        for (int w = 0; w < NT / 64; ++w) tsum += red[w];
-        partial[blockIdx.x] = tsum;
-    }
+    const float tsum = mk_block_sum_t0<NT>(s, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = tsum;
 }
 
 static long long pre_slots(const MkAdamTensor* pre, int npre) {

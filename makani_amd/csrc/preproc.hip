@@ -26,7 +26,7 @@
 // 8192; mk_prep_chunks sizes the workspaces for the finer cut.
 // 16-byte path (P = 4): HW a multiple of 4 and every pointer 16-byte aligned, so that every plane base is aligned for its
 // element type; otherwise one pixel per thread (P = 1).  All element offsets are 64-bit.
-#include "common.h"
+#include "block_io.h"
 
 namespace {
 
@@ -66,61 +66,17 @@ __device__ __forceinline__ void* p_at(void* base, int dt, long long e) {
     return dt == MK_BF16 ? (void*)((u16*)base + e) : (void*)((float*)base + e);
 }
 
+// the element type is a run-time value here
 template <int P>
 __device__ __forceinline__ void p_ld(const void* base, int dt, long long i, float (&v)[P]) {
-    if (dt == MK_BF16) {
-        const u16* p = (const u16*)base + i;
-        if constexpr (P == 4) {
-            const s16x4 t = *reinterpret_cast<const s16x4*>(p);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = bf16_to_f32((u16)t[k]);
-        } else {
-            v[0] = bf16_to_f32(*p);
-        }
-    } else {
-        const float* p = (const float*)base + i;
-        if constexpr (P == 4) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-            v[0] = t[0], v[1] = t[1], v[2] = t[2], v[3] = t[3];
-        } else {
-            v[0] = *p;
-        }
-    }
+    if (dt == MK_BF16) mk_ld<u16, P>((const u16*)base + i, v);
+    else mk_ld<float, P>((const float*)base + i, v);
 }
 
 template <int P>
 __device__ __forceinline__ void p_st(void* base, int dt, long long i, const float (&v)[P]) {
-    if (dt == MK_BF16) {
-        u16* p = (u16*)base + i;
-        if constexpr (P == 4) {
-            s16x4 t;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) t[k] = (short)f32_to_bf16(v[k]);
-            *reinterpret_cast<s16x4*>(p) = t;
-        } else {
-            *p = f32_to_bf16(v[0]);
-        }
-    } else {
-        float* p = (float*)base + i;
-        if constexpr (P == 4) {
-            const f32x4 t = {v[0], v[1], v[2], v[3]};
-            *reinterpret_cast<f32x4*>(p) = t;
-        } else {
-            *p = v[0];
-        }
-    }
-}
-
-// the block's sum of one per-thread value, returned to EVERY thread: wave shuffles, then the four waves in order
-__device__ __forceinline__ float p_block_sum(float v, float* red) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();          // (red may still be read from the previous sum)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float t = 0.f;
-#pragma unroll
-    for (int i = 0; i < PNT / 64; ++i) t += red[i];
-    return t;
+    if (dt == MK_BF16) mk_st<u16, P>((u16*)base + i, v);
+    else mk_st<float, P>((float*)base + i, v);
 }
 
 // pixels [c0, c1) of chunk `chunk`: `per` is a multiple of 4
@@ -165,8 +121,8 @@ __global__ __launch_bounds__(PNT) void prep_stats_kernel(PSrc s, const float* __
             }
         }
     }
-    W = p_block_sum(W, red);
-    S = p_block_sum(S, red);
+    W = mk_block_sum_all<PNT>(W, red);
+    S = mk_block_sum_all<PNT>(S, red);
     const float d = W > 0.f ? S / W : 0.f;
     float M2 = 0.f;
     for (int t = 0; t < s.T; ++t) {
@@ -185,7 +141,7 @@ __global__ __launch_bounds__(PNT) void prep_stats_kernel(PSrc s, const float* __
             }
         }
     }
-    M2 = p_block_sum(M2, red);
+    M2 = mk_block_sum_all<PNT>(M2, red);
     if (threadIdx.x == 0) dst[0] = W, dst[1] = K, dst[2] = d, dst[3] = M2;
 }
 
@@ -306,8 +262,8 @@ __global__ __launch_bounds__(PNT) void prep_bwd_sums_kernel(const void* __restri
             }
         }
     }
-    A = p_block_sum(A, red);
-    X = p_block_sum(X, red);
+    A = mk_block_sum_all<PNT>(A, red);
+    X = mk_block_sum_all<PNT>(X, red);
     if (threadIdx.x == 0) {
         float* dst = partial + ((long long)plane * gridDim.x + blockIdx.x) * 2;
         dst[0] = A, dst[1] = X;
@@ -339,8 +295,8 @@ __global__ __launch_bounds__(PNT) void prep_finish_bwd_kernel(const void* __rest
             X = fmaf(gv[e], bp ? v[e] - bv[e] : v[e], X);
         }
     }
-    A = p_block_sum(A, red);
-    X = p_block_sum(X, red);
+    A = mk_block_sum_all<PNT>(A, red);
+    X = mk_block_sum_all<PNT>(X, red);
     if (threadIdx.x == 0) {
         float* dst = partial + ((long long)plane * gridDim.x + blockIdx.x) * 2;
         dst[0] = A, dst[1] = X;
@@ -419,7 +375,6 @@ __global__ __launch_bounds__(PNT) void prep_bwd_apply_kernel(const void* __restr
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 bool dt_ok(int dt) { return dt == MK_F32 || dt == MK_BF16; }
 
 // the reduction kernels take four chunks of the streaming kernels at a time (their workspaces, sized with mk_prep_chunks, hold more)
@@ -454,7 +409,7 @@ int make_src(const char* what, PSrc& s, int& J, const void* win, int win_dt, con
     return 0;
 }
 
-bool src_vec(const PSrc& s, long long hw) { return hw % 4 == 0 && aligned16(s.win) && aligned16(s.unp) && aligned16(s.noi); }
+bool src_vec(const PSrc& s, long long hw) { return hw % 4 == 0 && mk_aligned16(s.win) && mk_aligned16(s.unp) && mk_aligned16(s.noi); }
 
 }  // namespace
 
@@ -475,7 +430,7 @@ extern "C" int mk_prep_stats(const void* win, int win_dt, const void* unp, int u
     const int chunks = red_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)(B * J));
-    if (src_vec(s, hw) && aligned16(q))
+    if (src_vec(s, hw) && mk_aligned16(q))
         hipLaunchKernelGGL((prep_stats_kernel<4>), grid, dim3(PNT), 0, st, s, q, wt, ws, J, hw, per);
     else
         hipLaunchKernelGGL((prep_stats_kernel<1>), grid, dim3(PNT), 0, st, s, q, wt, ws, J, hw, per);
@@ -500,7 +455,7 @@ extern "C" int mk_prep_assemble(const void* win, int win_dt, const void* unp, in
     const int chunks = mk_prep_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)(T * J + S), (unsigned)B);
-    if (src_vec(s, hw) && aligned16(stat) && aligned16(out))
+    if (src_vec(s, hw) && mk_aligned16(stat) && mk_aligned16(out))
         hipLaunchKernelGGL((prep_assemble_kernel<4>), grid, dim3(PNT), 0, st, s, stat, stat_dt, mu, sigma, out, out_dt, J, S, hw, per);
     else
         hipLaunchKernelGGL((prep_assemble_kernel<1>), grid, dim3(PNT), 0, st, s, stat, stat_dt, mu, sigma, out, out_dt, J, S, hw, per);
@@ -518,7 +473,7 @@ extern "C" int mk_prep_finish(const void* yn, int dtype, const float* bias, cons
     const int chunks = mk_prep_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)Cout, (unsigned)B);
-    if (hw % 4 == 0 && aligned16(yn) && aligned16(y) && aligned16(bias))
+    if (hw % 4 == 0 && mk_aligned16(yn) && mk_aligned16(y) && mk_aligned16(bias))
         hipLaunchKernelGGL((prep_finish_kernel<4>), grid, dim3(PNT), 0, st, yn, dtype, bias, mu, sigma, y, J, hw, per);
     else
         hipLaunchKernelGGL((prep_finish_kernel<1>), grid, dim3(PNT), 0, st, yn, dtype, bias, mu, sigma, y, J, hw, per);
@@ -539,7 +494,7 @@ extern "C" int mk_prep_bwd_sums(const void* g, int g_dt, const void* win, int wi
     const int chunks = red_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)(B * J));
-    if (src_vec(s, hw) && aligned16(g))
+    if (src_vec(s, hw) && mk_aligned16(g))
         hipLaunchKernelGGL((prep_bwd_sums_kernel<4>), grid, dim3(PNT), 0, st, g, g_dt, s, mu, sigma, ws, J, S, need, hw, per);
     else
         hipLaunchKernelGGL((prep_bwd_sums_kernel<1>), grid, dim3(PNT), 0, st, g, g_dt, s, mu, sigma, ws, J, S, need, hw, per);
@@ -568,7 +523,7 @@ extern "C" int mk_prep_bwd_apply(const void* g, int g_dt, const void* win, int w
     const int chunks = mk_prep_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)(T * J), (unsigned)B);
-    if (src_vec(s, hw) && aligned16(g) && aligned16(q) && aligned16(dwin) && aligned16(dnoi))
+    if (src_vec(s, hw) && mk_aligned16(g) && mk_aligned16(q) && mk_aligned16(dwin) && mk_aligned16(dnoi))
         hipLaunchKernelGGL((prep_bwd_apply_kernel<4>), grid, dim3(PNT), 0, st, g, g_dt, s, q, wt, mu, sigma, G, dwin, dnoi, B, J, S, hw, per);
     else
         hipLaunchKernelGGL((prep_bwd_apply_kernel<1>), grid, dim3(PNT), 0, st, g, g_dt, s, q, wt, mu, sigma, G, dwin, dnoi, B, J, S, hw, per);
@@ -587,7 +542,7 @@ extern "C" int mk_prep_finish_bwd(const void* g, int g_dt, const void* yn, int y
     const int chunks = red_chunks(hw);
     const long long per = per_chunk(hw, chunks);
     const dim3 grid((unsigned)chunks, (unsigned)(B * Cout));
-    if (hw % 4 == 0 && aligned16(g) && aligned16(yn) && aligned16(bias))
+    if (hw % 4 == 0 && mk_aligned16(g) && mk_aligned16(yn) && mk_aligned16(bias))
         hipLaunchKernelGGL((prep_finish_bwd_kernel<4>), grid, dim3(PNT), 0, st, g, g_dt, yn, yn_dt, bias, ws, Cout, hw, per);
     else
         hipLaunchKernelGGL((prep_finish_bwd_kernel<1>), grid, dim3(PNT), 0, st, g, g_dt, yn, yn_dt, bias, ws, Cout, hw, per);
