@@ -631,6 +631,29 @@ int mk_prep_bwd_apply(const void* g, int g_dtype, const void* win, int win_dtype
 int mk_prep_finish_bwd(const void* g, int g_dtype, const void* yn, int yn_dtype, const float* bias, float* gmu, float* gsig, float* ws,
                        int B, int Cout, int J, long long HW, void* stream);
 
+/* ---- online rollout diagnostics (csrc/rollout.hip; makani/utils/inference/rollout_buffer.py:670-1338) ----------------------
+ * Running mean and centred sum of squares (M2), fp32, updated in place by Welford's merge.  count: DEVICE pointer to the int64
+ * number of samples merged before this call; the kernels only read it, the caller adds B behind the launch on the same stream.
+ * With n0 = *count, n = n0 + B, d = mean_b - mean:  mean += d B / n,  m2 += m2_b + d^2 n0 B / n  (mean_b, m2_b: the batch's mean
+ * and centred M2 over b, any B >= 1).  Every element is written by one thread: repeats are bit-identical.
+ *   mk_welford_update: src (B, Csrc, N) f32 | bf16 read in place, y = scale[c] x[chan[c]] + bias[c] (chan (C) int32 device list of
+ *                      source channels, scale, bias (C) f32; NULL each: identity), mean, m2 (C, N).  16-byte accesses when N is a
+ *                      multiple of 4 and src, mean, m2 are 16-byte aligned, one point per thread otherwise.  C <= 65535.
+ *   mk_power_spectrum: S (L, M, 2, R) S-layout coefficients with row = (b E + e) Cp + c ->
+ *                      out[b][c][e0 + e][l] = sum_m c_m |scale[c] s + [m + m_off == 0] bias[c] one[l]|^2, out (B, C, E1, L) f32 | bf16,
+ *                      c_m = 1 for the global order 0 and 2 otherwise, orders m > l + tri_off not read (tri_off = l_off - m_off of
+ *                      a shard); one (L): the coefficients of the constant field 1 at order 0 (this shard's degrees).
+ *   mk_zonal_welford:  F (M, nlat, 2, R) longitude spectra (norm "forward") with row = (b E + e) Cp + c ->
+ *                      p_b = c_m latw[k] |scale[c] F + [m == 0] bias[c]|^2 (c_m = 2 for every m >= 1), rounded to bf16 when
+ *                      round_bf16, merged over b into mean, m2 (C, E1, nlat, M) at member e0 + e.  nlat <= 65535. */
+int mk_welford_update(const void* src, int dtype, const int* chan, const float* scale, const float* bias, float* mean, float* m2,
+                      const long long* count, int B, int Csrc, int C, long long N, void* stream);
+int mk_power_spectrum(const float* S, const float* scale, const float* bias, const float* one, void* out, int out_dtype, int L, int M,
+                      int R, int Cp, int B, int E, int C, int E1, int e0, int tri_off, int m_off, void* stream);
+int mk_zonal_welford(const float* F, const float* scale, const float* bias, const float* latw, float* mean, float* m2,
+                     const long long* count, int round_bf16, int M, int nlat, int R, int Cp, int B, int E, int C, int E1, int e0,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

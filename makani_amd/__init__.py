@@ -16,6 +16,7 @@ from .disco import DiscreteContinuousConvS2, ResampleS2
 from .fcn3 import AtmoSphericNeuralOperatorNet
 from .preprocessor import Preprocessor2D
 from .noise import BaseNoiseS2, IsotropicGaussianRandomFieldS2, DiffusionNoiseS2, DummyNoiseS2, InputNoise, build_noise, noise_seed_reflect
+from .rollout_buffer import MeanStdBuffer, TemporalAverageBuffer, SpectrumAverageBuffer, ZonalSpectrumAverageBuffer, power_spectrum
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DistributedRealVectorSHT", "DistributedInverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
@@ -27,4 +28,5 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
            "deterministic_sums",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
-           "noise_seed_reflect", "Preprocessor2D"]
+           "noise_seed_reflect", "Preprocessor2D",
+           "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum"]

@@ -152,6 +152,11 @@ _SIGS = {
     "mk_prep_bwd_apply": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
                            c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
     "mk_prep_finish_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_welford_update": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_power_spectrum": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_int, c_vp], c_int),
+    "mk_zonal_welford": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                          c_vp], c_int),
 }
 
 EXPORTS = sorted(list(_SIGS) + ["mk_last_error"])
