@@ -654,6 +654,50 @@ int mk_zonal_welford(const float* F, const float* scale, const float* bias, cons
                      const long long* count, int round_bf16, int M, int nlat, int R, int Cp, int B, int E, int C, int E1, int e0,
                      void* stream);
 
+/* ---- physical output constraints (csrc/constraints.hip; makani/models/parametrizations.py:193-231,
+ *      makani/utils/constraints.py:91-113,288-320) ------------------------------------------------------------------------------
+ * Pointwise in space: one thread per pixel, or per four consecutive pixels when HW is a multiple of 4 and every tensor pointer is
+ * 16-byte aligned.  x, y, g, gx are f32 | bf16 of ONE dtype, contiguous (B, C, HW); the arithmetic is fp32.  Channels a layer
+ * does not touch are copied in the same launch.  Nothing is read on the host: the launches can be captured in a graph.
+ *
+ * The column mix (hydrostatic wrapper and projection), x (B, Cin, HW) -> y (B, Cout, HW):
+ *     u_k = s_k x[in_ch[k]] + b_k (k < K_in);   f_j = 1 + eps (qs_j x[q_ch[j]] + qb_j) (j < NQ);   u_k *= f_k (k < n_mi)
+ *     v_r = [RESID] u_r + beta (sum_k M[r][k] u_k - off_r) (r < K_out);   v_r /= f_r (r < n_mo)
+ *     y[out_ch[r]] = (v_r - b'_r) / s'_r;   y[q_out[j]] = Q_ROUNDTRIP ? ((qs_j x + qb_j) - qb_j) / qs_j : x[q_ch[j]];
+ *     y[copy_dst[c]] = x[copy_src[c]] (c < NC)
+ * with K_in + NQ + NC = Cin and K_out + NQ + NC = Cout: the three lists partition the channels on either side.  K_in, K_out <=
+ * MK_CMIX_ROWS, n_mi, n_mo <= NQ <= MK_CMIX_LEVELS.  The two DEVICE tables hold, in this order,
+ *     itab (MK_CMIX_ITAB + 2 NC int32): in_ch, out_ch (MK_CMIX_ROWS each), q_ch, q_out (MK_CMIX_LEVELS each), copy_src, copy_dst (NC each);
+ *         the entries of the first four lists beyond their count must repeat a VALID channel (they are read, the value is dropped)
+ *     ftab (MK_CMIX_FTAB f32): s, b, s', b', off (MK_CMIX_ROWS each), qs, qb (MK_CMIX_LEVELS each), M and its transpose
+ *         (MK_CMIX_ROWS x MK_CMIX_ROWS each, row-major, zero beyond K_out x K_in); s, b, off are 0 and s', qs are 1 beyond their count;
+ *         then the folded map that the forward reads when NQ = 0 (x -> y is affine there): W = diag(1 / s') ([RESID] I + beta M) diag(s)
+ *         as a high and a low f32 limb (MK_CMIX_ROWS x MK_CMIX_ROWS each, W = high + low, zero beyond K_out x K_in) and
+ *         c = ([RESID] b + beta (M b - off) - b') / s' likewise (MK_CMIX_ROWS each), both computed in fp64.  y_r = sum_k W[r][k] x_k + c_r
+ *         is summed with error compensation and rounded once.
+ * The channel indices are NOT checked (the tables are device memory): the caller guarantees in_ch, q_ch, copy_src < Cin and
+ * out_ch, q_out, copy_dst < Cout.
+ *   mk_cmix_bwd: gx (B, Cin, HW) from g (B, Cout, HW), the transpose of the above; x is read when NQ > 0 only (the terms
+ *                through f), and may be NULL otherwise.
+ *
+ * Non-negativity on the channels with slot[c] >= 0 (slot (C) int32 device, offset (n) f32 device or NULL = 0), w = x + offset[slot[c]]:
+ *   mode 0: w sigmoid(w / eps) - offset;  mode 1: leak w + (1 - leak) eps (softplus(w / eps) - ln 2) - offset;  mode 2: max(x, -offset)
+ *   mk_nonneg_bwd: gx = g d/dx of the same. */
+#define MK_CMIX_ROWS 32
+#define MK_CMIX_LEVELS 16
+#define MK_CMIX_ITAB (2 * MK_CMIX_ROWS + 2 * MK_CMIX_LEVELS)
+#define MK_CMIX_FTAB (7 * MK_CMIX_ROWS + 2 * MK_CMIX_LEVELS + 4 * MK_CMIX_ROWS * MK_CMIX_ROWS)
+#define MK_CMIX_RESID 1
+#define MK_CMIX_Q_ROUNDTRIP 2
+int mk_cmix_fwd(const void* x, void* y, int dtype, const int* itab, const float* ftab, int B, int Cin, int Cout, int K_in, int K_out, int NQ,
+                int n_mi, int n_mo, int NC, int flags, float beta, float eps, long long HW, void* stream);
+int mk_cmix_bwd(const void* g, const void* x, void* gx, int dtype, const int* itab, const float* ftab, int B, int Cin, int Cout, int K_in,
+                int K_out, int NQ, int n_mi, int n_mo, int NC, int flags, float beta, float eps, long long HW, void* stream);
+int mk_nonneg_fwd(const void* x, void* y, int dtype, const int* slot, const float* offset, int mode, float eps, float leak, int B, int C,
+                  long long HW, void* stream);
+int mk_nonneg_bwd(const void* g, const void* x, void* gx, int dtype, const int* slot, const float* offset, int mode, float eps, float leak,
+                  int B, int C, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

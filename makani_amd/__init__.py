@@ -17,6 +17,8 @@ from .fcn3 import AtmoSphericNeuralOperatorNet
 from .preprocessor import Preprocessor2D
 from .noise import BaseNoiseS2, IsotropicGaussianRandomFieldS2, DiffusionNoiseS2, DummyNoiseS2, InputNoise, build_noise, noise_seed_reflect
 from .rollout_buffer import MeanStdBuffer, TemporalAverageBuffer, SpectrumAverageBuffer, ZonalSpectrumAverageBuffer, power_spectrum
+from .constraints import (ConstraintsWrapper, HydrostaticBalanceProjection, NonNegativeConstraint, constrain_model_handle,
+                          get_matching_channels_pl)
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DistributedRealVectorSHT", "DistributedInverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
@@ -29,4 +31,6 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "deterministic_sums",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
            "noise_seed_reflect", "Preprocessor2D",
-           "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum"]
+           "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum",
+           "ConstraintsWrapper", "HydrostaticBalanceProjection", "NonNegativeConstraint", "constrain_model_handle",
+           "get_matching_channels_pl"]

@@ -157,6 +157,12 @@ _SIGS = {
                            c_int, c_vp], c_int),
     "mk_zonal_welford": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                           c_vp], c_int),
+    "mk_cmix_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_ll,
+                     c_vp], c_int),
+    "mk_cmix_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f,
+                     c_ll, c_vp], c_int),
+    "mk_nonneg_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_nonneg_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
 }
 
 EXPORTS = sorted(list(_SIGS) + ["mk_last_error"])

@@ -1616,3 +1616,154 @@ class DistInstanceNormFn(torch.autograd.Function):
         dgamma = local[1] if g is not None else None
         dbeta = local[0] if b is not None else None
         return gx, dgamma, dbeta, None, None, None, None, None
+
+
+# ---- physical output constraints (csrc/constraints.hip) ---------------------------------------------------------------------
+CMIX_ROWS, CMIX_LEVELS = 32, 16          # MK_CMIX_ROWS, MK_CMIX_LEVELS of include/makani_amd.h
+CMIX_RESID, CMIX_Q_ROUNDTRIP = 1, 2
+
+
+@dataclass
+class ColumnMix:
+    """One descriptor of ``mk_cmix_fwd`` / ``mk_cmix_bwd`` (the layout of the two device tables is in include/makani_amd.h)"""
+    itab: torch.Tensor
+    ftab: torch.Tensor
+    Cin: int
+    Cout: int
+    K_in: int
+    K_out: int
+    NQ: int
+    n_mi: int
+    n_mo: int
+    NC: int
+    flags: int
+    beta: float
+    eps: float
+
+    def args(self):
+        return (self.Cin, self.Cout, self.K_in, self.K_out, self.NQ, self.n_mi, self.n_mo, self.NC, self.flags, self.beta, self.eps)
+
+
+def column_mix(in_ch, out_ch, q_ch, q_out, copy_src, copy_dst, in_s, in_b, out_s, out_b, off, q_s, q_b, M, Cin, Cout, n_mi, n_mo, resid,
+               q_roundtrip, beta, eps, device) -> ColumnMix:
+    """Build the descriptor: the channel lists are host lists (checked here: the kernels do not check them), the coefficient
+    vectors and ``M`` (K_out, K_in) are fp32 tensors on any device."""
+    K_in, K_out, NQ, NC = len(in_ch), len(out_ch), len(q_ch), len(copy_src)
+    if not (1 <= K_in <= CMIX_ROWS and 1 <= K_out <= CMIX_ROWS and NQ <= CMIX_LEVELS):
+        raise ValueError(f"the column kernels hold at most {CMIX_LEVELS} levels in registers ({K_in} -> {K_out} rows, {NQ} humidity rows)")
+    if sorted([*in_ch, *q_ch, *copy_src]) != list(range(Cin)) or sorted([*out_ch, *q_out, *copy_dst]) != list(range(Cout)) \
+            or len(q_out) != NQ or len(copy_dst) != NC:
+        raise ValueError("the gathered, humidity and copied channels must partition the input and the output channels")
+
+    def ipad(lst, n):
+        return list(lst) + [lst[-1] if lst else 0] * (n - len(lst))
+
+    def fpad(v, n, fill):
+        out = torch.full((n,), fill, dtype=torch.float32, device=device)
+        if v is not None and v.numel():
+            out[:v.numel()] = v.detach().reshape(-1).to(device=device, dtype=torch.float32)
+        return out
+
+    itab = torch.tensor(ipad(in_ch, CMIX_ROWS) + ipad(out_ch, CMIX_ROWS) + ipad(q_ch, CMIX_LEVELS) + ipad(q_out, CMIX_LEVELS)
+                        + list(copy_src) + list(copy_dst), dtype=torch.int32, device=device)
+    Mp = torch.zeros((CMIX_ROWS, CMIX_ROWS), dtype=torch.float32, device=device)
+    Mp[:K_out, :K_in] = M.detach().to(device=device, dtype=torch.float32)
+    # the dry forward is affine in x: y = W x + c, folded in fp64 from the fp32 vectors and split into two fp32 limbs
+    def f64(v, n, fill):
+        out = torch.full((n,), fill, dtype=torch.float64)
+        if v is not None and v.numel():
+            out[:v.numel()] = v.detach().reshape(-1).to(device="cpu", dtype=torch.float64)
+        return out
+
+    s_i, b_i, s_o, b_o, o_o = f64(in_s, K_in, 0.0), f64(in_b, K_in, 0.0), f64(out_s, K_out, 1.0), f64(out_b, K_out, 0.0), f64(off, K_out, 0.0)
+    G = float(beta) * M.detach().to(device="cpu", dtype=torch.float64).reshape(K_out, K_in)
+    c = G @ b_i - float(beta) * o_o - b_o
+    if resid:
+        n = min(K_in, K_out)
+        G = G + torch.eye(K_out, K_in, dtype=torch.float64)
+        c[:n] += b_i[:n]
+    W = torch.zeros((CMIX_ROWS, CMIX_ROWS), dtype=torch.float64)
+    W[:K_out, :K_in] = G * s_i[None, :] / s_o[:, None]
+    cv = torch.zeros(CMIX_ROWS, dtype=torch.float64)
+    cv[:K_out] = c / s_o
+
+    def limbs(v):
+        hi = v.float()
+        return [hi.reshape(-1).to(device), (v - hi.double()).float().reshape(-1).to(device)]
+
+    ftab = torch.cat([fpad(in_s, CMIX_ROWS, 0.0), fpad(in_b, CMIX_ROWS, 0.0), fpad(out_s, CMIX_ROWS, 1.0), fpad(out_b, CMIX_ROWS, 0.0),
+                      fpad(off, CMIX_ROWS, 0.0), fpad(q_s, CMIX_LEVELS, 1.0), fpad(q_b, CMIX_LEVELS, 0.0), Mp.reshape(-1),
+                      Mp.t().contiguous().reshape(-1), *limbs(W), *limbs(cv)])
+    flags = (CMIX_RESID if resid else 0) | (CMIX_Q_ROUNDTRIP if q_roundtrip else 0)
+    return ColumnMix(itab, ftab, Cin, Cout, K_in, K_out, NQ, n_mi, n_mo, NC, flags, float(beta), float(eps))
+
+
+def _planes(x, what):
+    """(B, C, H, W) contiguous f32 | bf16 (leading dimensions folded into B)"""
+    _lib.need_gpu(x, what)
+    if x.dim() < 3:
+        raise RuntimeError(f"{what}: expected (..., C, H, W), got {tuple(x.shape)}")
+    return _lib.prep(x)
+
+
+class ColumnMixFn(torch.autograd.Function):
+    """``mk_cmix_fwd`` and its transpose; the input is saved only by the moist forms (the dry ones are linear)"""
+
+    @staticmethod
+    def forward(ctx, x, d):
+        dtype_in = x.dtype
+        x = _planes(x, "constraints")
+        lead, hw = x.shape[:-3], x.shape[-2] * x.shape[-1]
+        B = int(np.prod(lead)) if lead else 1
+        if x.shape[-3] != d.Cin:
+            raise RuntimeError(f"the constraint expects {d.Cin} channels, got {x.shape[-3]}")
+        if d.itab.device != x.device:
+            raise RuntimeError("the constraint's tables live on another device than its input")
+        y = torch.empty((*lead, d.Cout, *x.shape[-2:]), dtype=x.dtype, device=x.device)
+        check(lib().mk_cmix_fwd(ptr(x), ptr(y), dtype_code(x), ptr(d.itab), ptr(d.ftab), B, *d.args(), hw, stream()), "mk_cmix_fwd")
+        ctx.d, ctx.B, ctx.hw, ctx.dtype_in = d, B, hw, dtype_in
+        ctx.save_for_backward(x if d.NQ > 0 else None)
+        ctx.in_shape = tuple(x.shape)
+        return y if y.dtype == dtype_in or dtype_in not in (torch.float16, torch.float64) else y.to(dtype_in)
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        d = ctx.d
+        dt = torch.bfloat16 if ctx.dtype_in == torch.bfloat16 else torch.float32
+        g = g.to(dt).contiguous()
+        gx = torch.empty(ctx.in_shape, dtype=dt, device=g.device)
+        check(lib().mk_cmix_bwd(ptr(g), ptr(x), ptr(gx), dtype_code(g), ptr(d.itab), ptr(d.ftab), ctx.B, *d.args(), ctx.hw, stream()),
+              "mk_cmix_bwd")
+        return (gx if gx.dtype == ctx.dtype_in else gx.to(ctx.dtype_in)), None
+
+
+class NonNegFn(torch.autograd.Function):
+    """``mk_nonneg_fwd`` / ``mk_nonneg_bwd``: ``slot`` (C) int32 names the clamped channels, ``mode`` 0 silu, 1 softplus, 2 hard"""
+
+    @staticmethod
+    def forward(ctx, x, slot, offset, mode, eps, leak):
+        dtype_in = x.dtype
+        x = _planes(x, "constraints")
+        C_, hw = x.shape[-3], x.shape[-2] * x.shape[-1]
+        B = x.numel() // (C_ * hw)
+        if slot.numel() != C_:
+            raise RuntimeError(f"the constraint expects {slot.numel()} channels, got {C_}")
+        if slot.device != x.device:
+            raise RuntimeError("the constraint's tables live on another device than its input")
+        y = torch.empty_like(x)
+        check(lib().mk_nonneg_fwd(ptr(x), ptr(y), dtype_code(x), ptr(slot), ptr(offset), mode, eps, leak, B, C_, hw, stream()),
+              "mk_nonneg_fwd")
+        ctx.meta = (mode, eps, leak, B, C_, hw, dtype_in)
+        ctx.save_for_backward(x, slot, offset)
+        return y if y.dtype == dtype_in or dtype_in not in (torch.float16, torch.float64) else y.to(dtype_in)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, slot, offset = ctx.saved_tensors
+        mode, eps, leak, B, C_, hw, dtype_in = ctx.meta
+        g = g.to(x.dtype).contiguous()
+        gx = torch.empty_like(x)
+        check(lib().mk_nonneg_bwd(ptr(g), ptr(x), ptr(gx), dtype_code(x), ptr(slot), ptr(offset), mode, eps, leak, B, C_, hw, stream()),
+              "mk_nonneg_bwd")
+        return (gx if gx.dtype == dtype_in else gx.to(dtype_in)), None, None, None, None, None

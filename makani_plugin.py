@@ -19,7 +19,7 @@ _ROOT = os.path.dirname(os.path.abspath(__file__))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from makani_amd import (AtmoSphericNeuralOperatorNet, MultiStepWrapper, SingleStepWrapper,  # noqa: E402,F401
+from makani_amd import (AtmoSphericNeuralOperatorNet, ConstraintsWrapper, MultiStepWrapper, SingleStepWrapper,  # noqa: E402,F401
                         SphericalFourierNeuralOperatorNet)
 
 

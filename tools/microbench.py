@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc] [constraints]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -622,6 +622,104 @@ def preproc():
                     print(f"preproc {mode:4s} n_history={nh}: statistics {ts:7.3f} ms {rate(b_stats, ts)} ({b_stats / 1e9:.2f} GB) | assemble "
                           f"launch {tasm:7.3f} ms {rate(b_asm, tasm)} ({b_asm / 1e9:.2f} GB)", flush=True)
                 del win, xz, static, bias, yn, pre
+
+
+def constraints():
+    """The output constraints (csrc/constraints.hip) at 721 x 1440, B = 1, C = 73 (8 surface channels, u v z t q on 13 levels),
+    forward + backward, f32 and bf16: the hydrostatic wrapper (61 -> 73 channels) and the projection, dry and moist, and the
+    "softplus" non-negativity clamp of the 13 q channels and tcwv; beside the reference's formulation in plain torch (gather,
+    .float(), scale and bias, a dense F.conv2d, divide, re-normalise, cast, index_copy; backward by autograd) on the same tensors
+    in the same process, the two timed in turn over three rounds, every timing over a window of at least 0.5 s.  Algorithmic
+    bytes: one read of the input and one write of the output per direction."""
+    import torch.nn.functional as F
+    from makani_amd import constraints as mc
+    PEAK = 8.0e12
+    H, W, B = 721, 1440, 1
+    N = H * W
+    levels = [50, 100, 150, 200, 250, 300, 400, 500, 600, 700, 850, 925, 1000]
+    names = ["u10m", "v10m", "u100m", "v100m", "t2m", "sp", "msl", "tcwv"] + [f"{v}{p}" for v in "uvztq" for p in levels]
+    C = len(names)
+    gen = torch.Generator().manual_seed(1)
+    bias, scale = torch.zeros(1, C, 1, 1), torch.ones(1, C, 1, 1)
+    for i, n in enumerate(names):
+        if n[1:].isdigit():
+            k = math.log(1000.0 / int(n[1:])) / math.log(20.0)
+            b, s = {"z": (600.0 + 6.9e4 * k, 3.0e3), "t": (285.0 - 70.0 * k, 15.0), "q": (2.0e-3, 2.0e-3), "u": (5.0, 10.0), "v": (0.0, 8.0)}[n[0]]
+            bias[0, i], scale[0, i] = b, s
+    EPS = mc.Q_CORRECTION_MOIST_AIR
+
+    def timed(fn):
+        once = max(timeit(fn, reps=3, warm=2), 1e-3)
+        return timeit(fn, reps=max(5, int(math.ceil(500.0 / once))), warm=1)
+
+    def torch_wrapper(m):
+        L, moist = m.num_levels, m.use_moist_air_formula
+        def f(x):
+            u = x.to(torch.float32) * m.inp_scale + m.inp_bias
+            if moist:
+                us = u.clone()
+                us[:, 0] = u[:, 0] * (1.0 + EPS * u[:, L + 1])
+                u = us
+            v = F.conv2d(u, m.mapping.unsqueeze(-1).unsqueeze(-1))
+            if moist:
+                v[:, m.t_idx] = v[:, m.t_idx] / (1.0 + EPS * v[:, m.q_idx])
+            return ((v - m.out_bias) / m.out_scale).to(x.dtype)
+        return f
+
+    def torch_projection(m):
+        L, moist = m.num_levels, m.use_moist_air_formula
+        def f(x):
+            xp = x[:, m.channel_indices].float() * m.scale_sub + m.bias_sub
+            if moist:
+                q = x[:, m.q_indices].float() * m.q_scale + m.q_bias
+                mult = torch.cat([1.0 + EPS * q, torch.ones_like(xp[:, L:])], dim=1)
+                xp = xp * mult
+            xp = xp - m.strength * (F.conv2d(xp, m.proj.unsqueeze(-1).unsqueeze(-1)) - m.off)
+            if moist:
+                xp = xp / mult
+            return x.index_copy(1, m.channel_indices, ((xp - m.bias_sub) / m.scale_sub).to(x.dtype))
+        return f
+
+    def torch_nonneg(m):
+        def f(x):
+            off = m.offset.to(x.dtype)
+            ws = x[:, m.channel_indices] + off
+            w = m.leak * ws + (1.0 - m.leak) * m.eps * (F.softplus(ws / m.eps) - math.log(2.0)) - off
+            return x.index_copy(1, m.channel_indices, w.to(x.dtype))
+        return f
+
+    layers = []
+    for moist in (False, True):
+        layers.append((f"wrapper {'moist' if moist else 'dry  '}", mc._HydrostaticBalanceWrapper(names, bias, scale, p_min=50, p_max=1000,
+                                                                                                use_moist_air_formula=moist), torch_wrapper))
+    for moist in (False, True):
+        layers.append((f"projection {'moist' if moist else 'dry  '}", mc.HydrostaticBalanceProjection(names, bias, scale, p_min=50, p_max=1000,
+                                                                                                   use_moist_air_formula=moist), torch_projection))
+    layers.append(("nonneg softplus", mc.NonNegativeConstraint(names, [f"q{p}" for p in levels] + ["tcwv"], bias, scale, mode="softplus"),
+                   torch_nonneg))
+    for label, mod, make in layers:
+        mod = mod.to(dev).train()
+        cin = mod.mapping.shape[1] if hasattr(mod, "mapping") else C
+        tfn = make(mod)
+        for dt in (torch.float32, torch.bfloat16):
+            x = torch.randn(B, cin, H, W, generator=gen).to(dt).to(dev).requires_grad_(True)
+            g = torch.randn(B, C, H, W, generator=gen).to(dt).to(dev)
+            nbytes = 2 * (cin + C) * B * N * x.element_size()
+
+            def ours():
+                return torch.autograd.grad(mod(x), x, g)[0]
+
+            def composed():
+                return torch.autograd.grad(tfn(x), x, g)[0]
+
+            err = ((mod(x).detach().float() - tfn(x).detach().float()).abs().max().item(),
+                   (ours().float() - composed().float()).abs().max().item())
+            for rnd in range(3):
+                t, tt = timed(ours), timed(composed)
+                print(f"constraints {label:16s} {str(dt)[6:]:8s} round {rnd}: forward + backward {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s "
+                      f"= {nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch formulation {tt:7.3f} ms = "
+                      f"{tt / t:5.2f} x | max |kernel - torch| {err[0]:.1e} {err[1]:.1e}", flush=True)
+            del x, g
 
 
 if __name__ == "__main__":
