@@ -698,6 +698,32 @@ int mk_nonneg_fwd(const void* x, void* y, int dtype, const int* slot, const floa
 int mk_nonneg_bwd(const void* g, const void* x, void* gx, int dtype, const int* slot, const float* offset, int mode, float eps, float leak,
                   int B, int C, long long HW, void* stream);
 
+/* ---- stochastic-interpolant stepper (csrc/interpolant.hip; makani/models/stochastic_interpolant.py:102-163,343-502) -----------
+ * Network input X (N, Cin, HW) with the channels [x0 (C) | x (C) | xu (U) | static (St) | s (has_s)], Cin = 2 C + U + St + has_s.
+ * Pointwise in space: one thread per pixel, or per four consecutive pixels when HW is a multiple of 4 and every tensor pointer is
+ * 16-byte aligned.  Tensors are f32 | bf16 by their dtype argument, contiguous; z, s and D are f32; the arithmetic is fp32.
+ * Nothing is read on the host, no workspace, no atomics: the launches can be captured in a graph.  B, Cin <= 65535.
+ *   mk_si_assemble: training.  x0, x1 (B, C, HW) of one dtype, z (B, C, HW), s (B, S') DEVICE memory, xu (B, U, HW), stat (St, HW)
+ *                   (NULL when U / St = 0).  Row n = b S' + j:  X[n][x0 slot] = x0[b],  X[n][x slot] = (1 - s) x0 + s^2 x1 + sqrt(s) eps (1 - s) z,
+ *                   D[n] (N, C, HW) = -x0 + 2 s x1 - eps sqrt(s) z,  X[n][xu slot] = xu[b],  X[n][static slot] = stat,  X[n][s slot] = s[b][j].
+ *                   The coefficients are two-float values formed in fp32 from s (eps: a double, split) and the sums are compensated:
+ *                   X and D are within fp32 rounding of the fp64 values of the fp32 inputs (two-float arithmetic: about 2^-44 relative
+ *                   before the final rounding), also where the terms cancel.
+ *   mk_si_step:     sampling.  out = X_next (B, Cin, HW): x0 slot = x0, x slot = cx x + cb b + c0 x0 + cn z, xu, static as above, s slot = s_next;
+ *                   x is read at x + b x_stride + c HW (elements: the x slot of the previous input, or x0 itself), b, x0, z (B, C, HW).
+ *                   b may be NULL when cb = 0, z when cn = 0 (cx = 1, the rest 0 writes the sampler's first input from x0 alone).
+ *                   last != 0: out = x_new (B, C, HW), the x slot alone (U, St, has_s are ignored).
+ *   mk_si_step_bwd: g the gradient of out (B, Cin, HW; last: (B, C, HW)):  gx0 = g[x0 slot] + c0 g[x slot] (last: c0 g),
+ *                   gx = cx g[x slot],  gb = cb g[x slot], each (B, C, HW), each optional (NULL). */
+int mk_si_assemble(const void* x0, const void* x1, int x_dtype, const float* z, const float* s, const void* xu, int xu_dtype,
+                   const void* stat, int stat_dtype, void* X, int out_dtype, float* D, double eps, int B, int Sp, int C, int U, int St,
+                   int has_s, long long HW, void* stream);
+int mk_si_step(const void* x, long long x_stride, int x_dtype, const void* b, int b_dtype, const void* x0, int x0_dtype, const float* z,
+               const void* xu, int xu_dtype, const void* stat, int stat_dtype, void* out, int out_dtype, float cx, float cb, float c0,
+               float cn, float s_next, int last, int B, int C, int U, int St, int has_s, long long HW, void* stream);
+int mk_si_step_bwd(const void* g, int g_dtype, void* gx0, int gx0_dtype, void* gx, int gx_dtype, void* gb, int gb_dtype, float cx, float cb,
+                   float c0, int last, int B, int C, int Cin, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,7 @@ from .noise import BaseNoiseS2, IsotropicGaussianRandomFieldS2, DiffusionNoiseS2
 from .rollout_buffer import MeanStdBuffer, TemporalAverageBuffer, SpectrumAverageBuffer, ZonalSpectrumAverageBuffer, power_spectrum
 from .constraints import (ConstraintsWrapper, HydrostaticBalanceProjection, NonNegativeConstraint, constrain_model_handle,
                           get_matching_channels_pl)
+from .interpolant import InterpolationWrapper, TimeAwareInterpolationWrapper, StochasticInterpolantWrapper
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DistributedRealVectorSHT", "DistributedInverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
@@ -33,4 +34,5 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "noise_seed_reflect", "Preprocessor2D",
            "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum",
            "ConstraintsWrapper", "HydrostaticBalanceProjection", "NonNegativeConstraint", "constrain_model_handle",
-           "get_matching_channels_pl"]
+           "get_matching_channels_pl",
+           "InterpolationWrapper", "TimeAwareInterpolationWrapper", "StochasticInterpolantWrapper"]

@@ -163,6 +163,11 @@ _SIGS = {
                      c_ll, c_vp], c_int),
     "mk_nonneg_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
     "mk_nonneg_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_si_assemble": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, C.c_double, c_int, c_int, c_int, c_int, c_int,
+                        c_int, c_ll, c_vp], c_int),
+    "mk_si_step": ([c_vp, c_ll, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_f, c_f, c_f, c_f, c_f, c_int,
+                    c_int, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
+    "mk_si_step_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
 }
 
 EXPORTS = sorted(list(_SIGS) + ["mk_last_error"])

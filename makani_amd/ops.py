@@ -1767,3 +1767,119 @@ class NonNegFn(torch.autograd.Function):
         check(lib().mk_nonneg_bwd(ptr(g), ptr(x), ptr(gx), dtype_code(x), ptr(slot), ptr(offset), mode, eps, leak, B, C_, hw, stream()),
               "mk_nonneg_bwd")
         return (gx if gx.dtype == dtype_in else gx.to(dtype_in)), None, None, None, None, None
+
+
+# ---- stochastic-interpolant stepper (csrc/interpolant.hip) ---------------------------------------------------------------------
+def _si_feat(t, shape, what):
+    """an optional feature tensor as contiguous f32 | bf16 of ``shape``; (pointer, dtype code, tensor kept alive)"""
+    if t is None:
+        return ptr(None), _lib.MK_F32, None
+    t = _lib.prep(t)
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"interpolant: {what} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return ptr(t), dtype_code(t), t
+
+
+def _si_out_dtype(out_dtype):
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"interpolant: the network input is written as float32 or bfloat16, not {out_dtype}")
+    return out_dtype
+
+
+def si_assemble(x0, x1, z, s, xu, static, eps, has_s=True, out_dtype=torch.float32):
+    """``mk_si_assemble``: x0, x1 (B, C, H, W) f32 | bf16, z (B, C, H, W), s (B, S') on the device, xu (B, U, H, W) | None, static
+    (St, H, W) | None -> the network input X (B S', 2 C + U + St + has_s, H, W) in ``out_dtype`` and the drift target D (B S', C, H, W) f32"""
+    _lib.need_gpu(x0, "interpolant")
+    x0 = _lib.prep(x0)
+    x1 = _lib.prep(x1.to(x0.dtype) if x1.dtype != x0.dtype else x1)
+    if x0.dim() != 4 or x1.shape != x0.shape or tuple(z.shape) != tuple(x0.shape):
+        raise RuntimeError(f"interpolant: x0 {tuple(x0.shape)}, x1 {tuple(x1.shape)} and z {tuple(z.shape)} are to be one (B, C, H, W)")
+    B, C_, H, W = x0.shape
+    if s.dim() != 2 or s.shape[0] != B:
+        raise RuntimeError(f"interpolant: s has shape {tuple(s.shape)}, expected ({B}, S')")
+    z, s = z.float().contiguous(), s.float().contiguous()
+    Sp, hw = s.shape[1], H * W
+    U = 0 if xu is None else xu.shape[-3]
+    St = 0 if static is None else static.shape[-3]
+    pu, du, xu = _si_feat(xu, (B, U, H, W), "xu")
+    ps, ds, static = _si_feat(static, (St, H, W), "static")
+    X = torch.empty((B * Sp, 2 * C_ + U + St + int(has_s), H, W), dtype=_si_out_dtype(out_dtype), device=x0.device)
+    D = torch.empty((B * Sp, C_, H, W), dtype=torch.float32, device=x0.device)
+    check(lib().mk_si_assemble(ptr(x0), ptr(x1), dtype_code(x0), ptr(z), ptr(s), pu, du, ps, ds, ptr(X), dtype_code(X), ptr(D), float(eps), B,
+                               Sp, C_, U, St, int(has_s), hw, stream()), "mk_si_assemble")
+    return X, D
+
+
+def _si_slot(x, what):
+    """``x`` (B, C, H, W) f32 | bf16 whose (C, H, W) blocks are dense (a channel slice of a network input, or a contiguous
+    tensor): read in place through its batch stride; anything else is copied"""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    if x.dim() != 4:
+        raise RuntimeError(f"interpolant: {what} has shape {tuple(x.shape)}, expected (B, C, H, W)")
+    _, C_, H, W = x.shape
+    if tuple(x.stride()[1:]) != (H * W, W, 1) or x.stride(0) < C_ * H * W:
+        x = x.contiguous()
+    return x
+
+
+def si_step(x, b, x0, z, xu, static, coef, s_next, last=False, has_s=True, out_dtype=torch.float32):
+    """``mk_si_step``: the next network input (B, Cin, H, W) with x slot = cx x + cb b + c0 x0 + cn z for ``coef = (cx, cb, c0, cn)``,
+    or x_new (B, C, H, W) alone when ``last``.  ``x`` may be the x slot of the previous input (a channel slice, read in place);
+    ``b`` / ``z`` may be None when their coefficient is zero."""
+    _lib.need_gpu(x0, "interpolant")
+    cx, cb, c0, cn = (float(v) for v in coef)
+    x, x0 = _si_slot(x, "x"), _lib.prep(x0)
+    B, C_, H, W = x0.shape
+    if tuple(x.shape) != (B, C_, H, W):
+        raise RuntimeError(f"interpolant: x {tuple(x.shape)} and x0 {tuple(x0.shape)} differ")
+    if (b is None and cb != 0.0) or (z is None and cn != 0.0):
+        raise RuntimeError("interpolant: a non-zero coefficient needs its field (b for cb, z for cn)")
+    b = None if b is None else _lib.prep(b)
+    z = None if z is None else z.float().contiguous()
+    for t, what in ((b, "b"), (z, "z")):
+        if t is not None and tuple(t.shape) != (B, C_, H, W):
+            raise RuntimeError(f"interpolant: {what} has shape {tuple(t.shape)}, expected {(B, C_, H, W)}")
+    U = 0 if (xu is None or last) else xu.shape[-3]
+    St = 0 if (static is None or last) else static.shape[-3]
+    pu, du, xu = _si_feat(None if last else xu, (B, U, H, W), "xu")
+    ps, ds, static = _si_feat(None if last else static, (St, H, W), "static")
+    chans = C_ if last else 2 * C_ + U + St + int(has_s)
+    out = torch.empty((B, chans, H, W), dtype=_si_out_dtype(out_dtype), device=x0.device)
+    check(lib().mk_si_step(ptr(x), x.stride(0), dtype_code(x), ptr(b), _lib.MK_F32 if b is None else dtype_code(b), ptr(x0), dtype_code(x0),
+                           ptr(z), pu, du, ps, ds, ptr(out), dtype_code(out), cx, cb, c0, cn, float(s_next), int(last), B, C_, U, St,
+                           int(has_s), H * W, stream()), "mk_si_step")
+    return out
+
+
+def si_step_bwd(g, coef, C_, last, want, dtypes):
+    """``mk_si_step_bwd``: (g_x0, g_x, g_b), each (B, C, H, W) in its dtype of ``dtypes`` or None where ``want`` says so"""
+    g = _lib.prep(g)
+    B, Cin, H, W = g.shape
+    outs = [torch.empty((B, C_, H, W), dtype=dt, device=g.device) if w else None for w, dt in zip(want, dtypes)]
+    if any(w for w in want):
+        args = []
+        for o in outs:
+            args += [ptr(o), _lib.MK_F32 if o is None else dtype_code(o)]
+        check(lib().mk_si_step_bwd(ptr(g), dtype_code(g), *args, float(coef[0]), float(coef[1]), float(coef[2]), int(last), B, C_, Cin, H * W,
+                                   stream()), "mk_si_step_bwd")
+    return outs
+
+
+class SiStepFn(torch.autograd.Function):
+    """One step of the interpolant's SDE sampler: ``si_step`` and ``si_step_bwd``.  Gradients go to x, b and x0."""
+
+    @staticmethod
+    def forward(ctx, x, b, x0, z, xu, static, coef, s_next, last, has_s, out_dtype):
+        out = si_step(x, b, x0, z, xu, static, coef, s_next, last, has_s, out_dtype)
+        ctx.meta = (coef, x0.shape[1], bool(last), tuple(t.dtype if t is not None and t.dtype == torch.bfloat16 else torch.float32
+                                                            for t in (x0, x, b)), tuple(None if t is None else t.dtype for t in (x0, x, b)))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        coef, C_, last, dts, orig = ctx.meta
+        need = ctx.needs_input_grad
+        gx0, gx, gb = si_step_bwd(g, coef, C_, last, (need[2], need[0], need[1]), dts)
+        gx0, gx, gb = (t if t is None or t.dtype == o else t.to(o) for t, o in zip((gx0, gx, gb), orig))
+        return gx, gb, gx0, None, None, None, None, None, None, None, None

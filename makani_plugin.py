@@ -20,7 +20,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from makani_amd import (AtmoSphericNeuralOperatorNet, ConstraintsWrapper, MultiStepWrapper, SingleStepWrapper,  # noqa: E402,F401
-                        SphericalFourierNeuralOperatorNet)
+                        SphericalFourierNeuralOperatorNet, StochasticInterpolantWrapper)
 
 
 def register(name: str = "SFNO_mi355x") -> None:

@@ -1,0 +1,124 @@
+"""The stochastic-interpolant sampler on a sphere split over h ranks (``StochasticInterpolantWrapper.from_params`` with the
+spatial group behind it), two processes sharing cuda:0 over gloo in the pattern of tests/test_gpu_noise_dist.py.
+
+Everything but the noise is pointwise in space, and the noise of ranks that share a seed is the shard of the serial field: each
+rank's 2-step sample is the slice of the serial sample within the relative 1e-5 that test_gpu_noise_dist.py uses for synthesised
+fields.  Grid 37 x 72, h = 2: the latitudes split [19, 18].  The generator of the interpolant times is seeded without the
+model-rank term, so both ranks would draw the same s.  Each process runs under its own time limit; a failing rank ends the test."""
+import os
+import socket
+import sys
+import time
+
+import pytest
+import torch
+import torch.distributed as dist
+import torch.multiprocessing as mp
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+IMG, B, C, U, ST = (37, 72), 2, 3, 2, 2
+TOL = 1e-5
+LIMIT = 240.0          # seconds per process, far above the few seconds a rank needs
+
+
+def _free_port():
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        return s.getsockname()[1]
+
+
+def _rel(a, b):
+    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
+
+
+class _Params(dict):
+    def __getattr__(self, k):
+        try:
+            return self[k]
+        except KeyError:
+            raise AttributeError(k)
+
+
+def _build(ma, static, foellmer):
+    """the wrapper from the reference's keys around the pointwise stub, from fixed seeds"""
+    from _preproc_ref import seeded
+    H, W = IMG
+    params = _Params(img_shape_x=H, img_shape_y=W, img_shape_x_resampled=H, img_shape_y_resampled=W, img_crop_shape_x=H, img_crop_shape_y=W,
+                     n_history=0, n_future=0, N_in_predicted_channels=C, N_out_channels=C, N_static_channels=ST, N_dynamic_channels=U,
+                     batch_size=B, data_grid_type="equiangular", model_grid_type="equiangular")
+
+    def handle(inp_chans):
+        conv = torch.nn.Conv2d(inp_chans, C, 1)
+        with torch.no_grad():
+            conv.weight.copy_(0.3 * seeded(conv.weight.shape, 61))
+            conv.bias.copy_(0.1 * seeded(conv.bias.shape, 62))
+        return conv
+
+    return ma.StochasticInterpolantWrapper.from_params(params, handle, noise_epsilon=0.7, use_foellmer=foellmer, seed=41, static_features=static)
+
+
+def _worker(rank, world, port, h, w):
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _fullsize import share_gpu
+    share_gpu(rank, world)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import makani_amd as ma
+        import makani_amd.comm as mcomm
+        import makani_amd.distributed as thd
+        from _preproc_ref import seeded
+        dev = torch.device("cuda:0")
+        x0 = seeded((B, C, *IMG), 71).float().to(dev)
+        xu = seeded((B, 1, U, *IMG), 72).float().to(dev)
+        static = seeded((1, ST, *IMG), 73).float()
+
+        def sample(mod, grid):
+            mod = mod.to(dev).eval()
+            mod.preprocessor.cache_unpredicted_features(None, None, xu[grid].contiguous(), None)
+            with torch.no_grad():
+                return mod(x0[grid].contiguous(), n_steps=2)
+
+        # ---- serial, from the same seeds, before the groups are initialised
+        everything = (Ellipsis, slice(None), slice(None))
+        serial = {f: _build(ma, static, f) for f in (False, True)}
+        assert not any(m.noise_module.spatial_parallel for m in serial.values())
+        want = {f: sample(m, everything) for f, m in serial.items()}
+        with torch.no_grad():          # the noise carries an O(1) share of the sample: what is compared below is not the drift alone
+            quiet = serial[False](x0, n_steps=2, noise=torch.zeros(2, B, C, *IMG, device=dev))
+        assert bool((want[False] - quiet).abs().max() > 0.1)
+
+        # ---- the same wrappers on the split sphere
+        _, ih, iw = mcomm.init(h, w)
+        assert thd.ensure_initialized()
+        probe = _build(ma, static, False).noise_module
+        assert probe.spatial_parallel and (probe.nlat_local, probe.nlon_local) == (([19, 18][ih] if h == 2 else 37), ([36, 36][iw] if w == 2 else 72))
+        grid = (Ellipsis, slice(probe.lat_off, probe.lat_off + probe.nlat_local), slice(probe.lon_off, probe.lon_off + probe.nlon_local))
+        for f in (False, True):
+            mod = _build(ma, static[grid].contiguous(), f)
+            assert mod.noise_module.spatial_parallel and mod.noise_module.rng.tolist() == serial[f].noise_module.rng.tolist()[:1] + [0]
+            assert mod._rng_seed == serial[f]._rng_seed == 41 + 333          # no model-rank term: the ranks draw the same s
+            y = sample(mod, grid)
+            assert tuple(y.shape) == (B, C, probe.nlat_local, probe.nlon_local) and bool(want[f][grid].abs().max() > 1e-3)
+            e = _rel(y, want[f][grid])
+            print(f"h{h}w{w} rank {rank} foellmer {f}: sample rel {e:.1e}", flush=True)
+            assert e < TOL, (rank, f, e)
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def test_split_sampler_gives_the_slices_of_the_serial_sample():
+    h, w = 2, 1
+    ctx = mp.spawn(_worker, args=(h * w, _free_port(), h, w), nprocs=h * w, join=False)
+    deadline = time.monotonic() + LIMIT
+    try:
+        while not ctx.join(timeout=max(0.1, deadline - time.monotonic())):          # raises when a rank failed, and ends the others
+            assert time.monotonic() < deadline, f"a rank ran into its time limit of {LIMIT:.0f} s"
+    finally:
+        for p in ctx.processes:
+            if p.is_alive():
+                p.kill()

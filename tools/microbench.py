@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc] [constraints]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc] [constraints] [interpolant]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -720,6 +720,101 @@ def constraints():
                       f"= {nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch formulation {tt:7.3f} ms = "
                       f"{tt / t:5.2f} x | max |kernel - torch| {err[0]:.1e} {err[1]:.1e}", flush=True)
             del x, g
+
+
+def interpolant():
+    """The stochastic-interpolant stepper (csrc/interpolant.hip) at 721 x 1440, C = 73, B = 1, U = 1, St = 3, fp32: the training
+    assemble for S' = 4 time samples (one launch) and one Foellmer sampler step (one launch), each beside the reference's op
+    sequence in plain torch on the same tensors in the same process (expand_time's repeats, the two three-term broadcasts, tile and
+    cat; for the step bhat, the score correction, the noise term and the cat of the next input), the two timed in turn over three
+    rounds, every timing over a window of at least 0.5 s.  Algorithmic bytes: every source read once, every output written once.
+    The torch sequence's compute ops are counted by a dispatch mode (views left out): each is at least one launch."""
+    from torch.utils._python_dispatch import TorchDispatchMode
+    from makani_amd.interpolant import step_coefficients
+    PEAK = 8.0e12
+    H, W, B, C, U, St, Sp, eps = 721, 1440, 1, 73, 1, 3, 4, 0.7
+    N, Cin = H * W, 2 * C + U + St + 1
+    gen = torch.Generator().manual_seed(1)
+    x0, x1, z, bnet = (torch.randn(B, C, H, W, generator=gen).to(dev) for _ in range(4))
+    xu, static = torch.randn(B, U, H, W, generator=gen).to(dev), torch.randn(1, St, H, W, generator=gen).to(dev)
+    s = torch.rand(B, Sp, generator=gen).to(dev)
+    VIEWS = ("view", "reshape", "expand", "unsqueeze", "squeeze", "slice", "select", "alias", "detach", "transpose", "permute", "as_strided", "t.")
+
+    class Count(TorchDispatchMode):
+        n = 0
+
+        def __torch_dispatch__(self, func, types, args=(), kwargs=None):
+            if not any(v in str(func) for v in VIEWS):
+                Count.n += 1
+            return func(*args, **(kwargs or {}))
+
+    def counted(fn):
+        Count.n = 0
+        with Count():
+            fn()
+        return Count.n
+
+    def timed(fn):
+        once = max(timeit(fn, reps=3, warm=2), 1e-3)
+        return timeit(fn, reps=max(5, int(math.ceil(500.0 / once))), warm=1)
+
+    def expand_time(x, n):
+        return x.unsqueeze(1).repeat(1, n, *[1] * (x.dim() - 1))
+
+    sig = lambda t: eps * (1.0 - t)
+
+    def torch_train():
+        inpu = expand_time(xu, Sp).flatten(0, 1)
+        stat = expand_time(torch.tile(static, (B, 1, 1, 1)), Sp).flatten(0, 1)
+        a, t = expand_time(x0, Sp), expand_time(x1, Sp)
+        noise = z.unsqueeze(1)
+        sr = s.reshape(B, Sp, 1, 1, 1)
+        inter = (1.0 - sr) * a + torch.square(sr) * t + (torch.sqrt(sr) * sig(sr)) * noise
+        drift = -1.0 * a + (2.0 * sr) * t + (torch.sqrt(sr) * (-1.0 * eps)) * noise
+        sp = torch.tile(s.flatten().reshape(-1, 1, 1, 1), (1, 1, H, W))
+        return torch.cat([a.flatten(0, 1), inter.flatten(0, 1), inpu, stat, sp], dim=-3), drift.flatten(0, 1)
+
+    def ours_train():
+        return ops.si_assemble(x0, x1, z, s, xu, static[0], eps)
+
+    si, ds = 0.5, 0.25
+    sv = torch.full((B, 1, 1, 1), si, device=dev)
+    dsv = torch.tensor(ds, device=dev)
+    coef = step_coefficients(si, ds, eps, foellmer=True)
+    x_prev = ours_train()[0][:B].contiguous()
+
+    def torch_step():
+        x, b = x_prev[:, C:2 * C], bnet
+        sg = sig(sv)
+        gsq = torch.abs(2.0 * torch.square(sg) * torch.where(sv > 0, sv * (2.0 * sv) / torch.square(sv), 2.0) - 2.0 * sv * sg * (-1.0 * eps)
+                        - torch.square(sg))
+        As = 1.0 / (sv * sg * ((2.0 * sv) * sg - torch.square(sv) * (-1.0 * eps)))
+        cs = x * (2.0 * sv) + (torch.square(sv) * -1.0 - (2.0 * sv) * (1.0 - sv)) * x0
+        bhat = b + 0.5 * (gsq - torch.square(sg)) * (As * (torch.square(sv) * b - cs))
+        xn = x + bhat * dsv
+        xn = xn + torch.sqrt(gsq * dsv) * z
+        sp = torch.tile(torch.full((B,), si + ds, device=dev).reshape(-1, 1, 1, 1), (1, 1, H, W))
+        return torch.cat([x0, xn, xu, static.expand(B, -1, -1, -1), sp], dim=-3)
+
+    def ours_step():
+        return ops.si_step(x_prev[:, C:2 * C], bnet, x0, z, xu, static[0], coef, si + ds)
+
+    b_train = 4 * N * (B * (3 * C + U) + St + B * Sp * (Cin + C))
+    b_step = 4 * N * (B * (4 * C + U) + St + B * Cin)
+    Xo, Do = ours_train()
+    Xt, Dt = torch_train()
+    e_train = ((Xo - Xt).abs().max().item(), (Do - Dt).abs().max().item())
+    e_step = (ours_step() - torch_step()).abs().max().item()
+    del Xo, Do, Xt, Dt
+    n_train, n_step = counted(torch_train), counted(torch_step)
+    for label, ours, composed, nbytes, nops, err in (("training assemble S'=4", ours_train, torch_train, b_train, n_train, e_train),
+                                                     ("sampler step (Foellmer)", ours_step, torch_step, b_step, n_step, e_step)):
+        for rnd in range(3):
+            t, tt = timed(ours), timed(composed)
+            print(f"interpolant {label:24s} round {rnd}: 1 launch {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s = "
+                  f"{nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch sequence, {nops} compute ops, "
+                  f"{tt:7.3f} ms = {nbytes / (tt * 1e-3) / 1e12:5.2f} TB/s of the same bytes = {tt / t:5.2f} x | max |kernel - torch| {err}",
+                  flush=True)
 
 
 if __name__ == "__main__":
