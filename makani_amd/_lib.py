@@ -1,176 +1,139 @@
-"""ctypes binding of libmakani_amd.so (the C ABI in include/makani_amd.h).
+"""ctypes binding of libmakani_amd.so, derived from the C ABI in include/makani_amd.h.
+
+The header is parsed once, at import: its ``#define MK_*`` integer constants (``CONSTS``), its descriptor structs as
+``ctypes.Structure`` classes (``STRUCTS``) and every prototype as ``(argtypes, restype)`` (``_SIGS``).  Nothing of the
+interface is written down here a second time: a new entry point is its prototype in the header and its definition in
+``csrc``.  A declaration the parser does not understand raises at import, naming the line.
 
 The product path has no CPU fallback: if the shared library is missing or a
 tensor is not on a GPU, calls raise.  Build with ``python -m makani_amd.build``.
 """
+import ast
 import ctypes as C
+import operator
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = os.path.join(_HERE, "..", "include", "makani_amd.h")          # the C ABI: the binding below and build.py's dependency check
 # MAKANI_AMD_LIB: a variant of the library built by tools/ab.py (same-box A/B measurements); default: the in-tree build
 LIB_PATH = os.environ.get("MAKANI_AMD_LIB") or os.path.join(_HERE, "libmakani_amd.so")
 
-MK_F32, MK_BF16 = 0, 1
-TRI_NONE, TRI_ROW_GE, TRI_K_GE, TRI_ROW_LE, TRI_K_LE = 0, 1, 2, 3, 4
+c_vp = C.c_void_p
 
-c_ll, c_int, c_f, c_vp = C.c_longlong, C.c_int, C.c_float, C.c_void_p
-
-
-class MkAdamTensor(C.Structure):
-    """mirrors `struct MkAdamTensor` of include/makani_amd.h"""
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_longlong),
-                ("p_bf16", C.c_void_p), ("p_bf16_t", C.c_void_p), ("cols", C.c_int), ("ld", C.c_int), ("ld_t", C.c_int)]
+_SCALARS = {"int": C.c_int, "long long": C.c_longlong, "float": C.c_float, "double": C.c_double}
+_OPS = {ast.Add: operator.add, ast.Sub: operator.sub, ast.Mult: operator.mul}
 
 
-class MkGemm(C.Structure):
-    _fields_ = [
-        ("A", c_vp), ("B", c_vp), ("C", c_vp),
-        ("a_batch", c_ll), ("a_row", c_ll), ("a_k", c_ll),
-        ("b_batch", c_ll), ("b_col", c_ll), ("b_k", c_ll),
-        ("c_batch", c_ll), ("c_row", c_ll), ("c_col", c_ll),
-        ("a_inner", c_ll), ("b_inner", c_ll), ("c_inner", c_ll),
-        ("a_im", c_ll), ("b_im", c_ll), ("c_im", c_ll),
-        ("M", c_int), ("N", c_int), ("K", c_int), ("batch", c_int),
-        ("inner", c_int), ("tri_mode", c_int), ("tri_off", c_int),
-        ("conj_a", c_int), ("conj_b", c_int), ("beta", c_int),
-    ]
+def _const_expr(expr, names):
+    """value of an integer constant expression: literals, the names known so far, + - * and parentheses, nothing else"""
+    def ev(n):
+        if isinstance(n, ast.Constant) and type(n.value) is int:
+            return n.value
+        if isinstance(n, ast.Name) and n.id in names:
+            return names[n.id]
+        if isinstance(n, ast.UnaryOp) and isinstance(n.op, (ast.USub, ast.UAdd)):
+            return -ev(n.operand) if isinstance(n.op, ast.USub) else ev(n.operand)
+        if isinstance(n, ast.BinOp) and type(n.op) in _OPS:
+            return _OPS[type(n.op)](ev(n.left), ev(n.right))
+        raise ValueError(f"{expr.strip()!r} is not an integer constant expression"
+                         + (f" (unknown name {n.id})" if isinstance(n, ast.Name) else ""))
+    try:
+        return ev(ast.parse(expr.strip(), mode="eval").body)
+    except SyntaxError:
+        raise ValueError(f"{expr.strip()!r} is not an integer constant expression") from None
 
 
-MK_FFT_SEG_MAX = 8
+def _ctype(spec, structs, ret=False):
+    """the ctypes type of a type as the header spells it ("long long", "const float*", "const MkGemm*")"""
+    words = [w for w in spec.replace("*", " * ").split() if w != "const"]
+    base, stars = " ".join(w for w in words if w != "*"), words.count("*")
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars == 1 and base in structs:
+        return C.POINTER(structs[base])
+    if stars == 1 and (base in _SCALARS or base == "void"):
+        return C.c_void_p
+    if ret and (base, stars) in (("char", 1), ("void", 0)):
+        return C.c_char_p if stars else None
+    raise ValueError(f"type {' '.join(spec.split())!r} is outside the vocabulary of the header")
 
 
-class MkFftSeg(C.Structure):
-    """mirrors `struct MkFftSeg` of include/makani_amd.h"""
-    _fields_ = [("nw", c_int), ("nh", c_int), ("m_off", c_int * (MK_FFT_SEG_MAX + 1)), ("r_off", c_int * (MK_FFT_SEG_MAX + 1)),
-                ("base", (c_ll * MK_FFT_SEG_MAX) * MK_FFT_SEG_MAX), ("xseg", c_int), ("x_stride", c_ll), ("x_nlat", c_int)]
+def parse_header(text, name="makani_amd.h"):
+    """(constants, structs, prototypes) of the header ``text``: {MK_NAME: int}, {struct name: ctypes.Structure class},
+    {function: (argtypes, restype)}.  Raises ValueError naming the line of whatever it does not understand."""
+    def blank(m):
+        return re.sub(r"[^\n]", " ", m.group())          # positions and line numbers stay those of the file
+
+    def fail(pos, msg):
+        return ValueError(f"{name}:{text.count(chr(10), 0, pos) + 1}: {msg}")
+
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", blank, text, flags=re.S)
+    consts, structs, protos = {}, {}, {}
+    for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(MK_\w+)[ \t]+(\S.*)$", text, re.M):
+        try:
+            consts[m.group(1)] = _const_expr(m.group(2), consts)
+        except ValueError as e:
+            raise fail(m.start(), f"{m.group(1)}: {e}") from None
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus.*?^[ \t]*#endif", blank, text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#.*$", blank, text, flags=re.M)
+    ndecl = len(re.findall(r"\bmk_\w*\s*\(", text))
+
+    for m in re.finditer(r"typedef\s+struct\s+(\w+)\s*\{(.*?)\}\s*\1\s*;", text, re.S):
+        fields, pos = [], m.start(2)
+        for decl in m.group(2).split(";")[:-1]:
+            first, *more = decl.split(",")
+            d = re.fullmatch(r"\s*(.*?)(\w+)\s*((?:\[[^\]]*\]\s*)*)", first, re.S)
+            try:
+                if not d or any("*" in x for x in more):
+                    raise ValueError(f"cannot read the field declaration {' '.join(decl.split())!r}")
+                base = C.c_void_p if "*" in d.group(1) else _ctype(d.group(1), {})
+                for x in [d.group(2) + d.group(3)] + more:
+                    fname, t = re.match(r"\s*(\w*)", x).group(1), base
+                    if not re.fullmatch(r"\s*\w+\s*(\[[^\]]*\]\s*)*", x):
+                        raise ValueError(f"cannot read the declarator {x.strip()!r}")
+                    for extent in reversed(re.findall(r"\[([^\]]*)\]", x)):
+                        t = t * _const_expr(extent, consts)
+                    fields.append((fname, t))
+            except ValueError as e:
+                raise fail(pos + len(decl) - len(decl.lstrip()), f"struct {m.group(1)}: {e}") from None
+            pos += len(decl) + 1
+        structs[m.group(1)] = type(m.group(1), (C.Structure,), {"_fields_": fields, "__doc__": f"`struct {m.group(1)}` of {name}"})
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{.*?\}\s*\1\s*;", blank, text, flags=re.S)
+
+    pos = 0
+    for stmt in text.split(";"):
+        at, pos = pos + len(stmt) - len(stmt.lstrip()), pos + len(stmt) + 1
+        if not stmt.strip():
+            continue
+        m = re.fullmatch(r"\s*([^()]+?)\b(mk_\w*)\s*\(([^()]*)\)\s*", stmt, re.S)
+        if not m:
+            raise fail(at, f"not a prototype: {' '.join(stmt.split())[:80]!r}")
+        try:
+            params = [] if m.group(3).strip() == "void" else m.group(3).split(",")
+            args = []
+            for p in params:
+                d = re.fullmatch(r"\s*(.*?)(\w+)\s*", p, re.S)
+                if not d or not d.group(1).strip():
+                    raise ValueError(f"cannot read the parameter {' '.join(p.split())!r}")
+                args.append(_ctype(d.group(1), structs))
+            protos[m.group(2)] = (args, _ctype(m.group(1), structs, ret=True))
+        except ValueError as e:
+            raise fail(at, f"{m.group(2)}: {e}") from None
+    if len(protos) != ndecl:
+        raise ValueError(f"{name}: understood {len(protos)} prototypes, but the header declares {ndecl} mk_...( entry points")
+    return consts, structs, protos
 
 
-_SIGS = {
-    "mk_version": ([], c_int),
-    "mk_sgemm_batched": ([C.POINTER(MkGemm), c_vp], c_int),
-    "mk_cgemm_batched": ([C.POINTER(MkGemm), c_vp], c_int),
-    "mk_sgemm_split_batched": ([C.POINTER(MkGemm), c_int, c_vp], c_int),
-    "mk_cgemm_split_batched": ([C.POINTER(MkGemm), c_int, c_vp], c_int),
-    "mk_cgemm_split2_batched": ([C.POINTER(MkGemm), c_int, c_vp], c_int),
-    "mk_cgemm_split2_ssq_count": ([C.POINTER(MkGemm)], c_ll),
-    "mk_cgemm_split2_batched_ssq": ([C.POINTER(MkGemm), c_int, c_vp, c_vp], c_int),
-    "mk_sgemm_presplit_batched": ([C.POINTER(MkGemm), c_vp, c_ll, c_ll, c_ll, c_int, c_vp, c_vp, c_int, c_vp], c_int),
-    "mk_vlegendre": ([c_vp, c_vp, c_ll, c_ll, c_ll, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp], c_int),
-    "mk_vcols_repack": ([c_vp, c_vp, c_ll, c_ll, c_int, c_int, c_ll, c_int, c_int, c_ll, c_int, c_int, c_int, c_vp], c_int),
-    "mk_rfft_rows": ([c_vp, c_int, c_vp, c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                      c_f, c_f, c_f, c_vp], c_int),
-    "mk_irfft_rows": ([c_vp, c_vp, c_int, c_vp, C.POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                       c_f, c_f, c_f, c_vp], c_int),
-    "mk_fft_seg_supported": ([c_int], c_int),
-    "mk_rfft_rows_seg": ([c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, C.POINTER(MkFftSeg), c_vp], c_int),
-    "mk_irfft_rows_seg": ([c_vp, c_vp, c_int, c_vp, c_int, c_int, c_int, c_int, c_f, c_f, c_f, C.POINTER(MkFftSeg), c_vp], c_int),
-    "mk_weight_to_wlayout": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_wlayout_to_weight_grad": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_slayout_to_complex": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_complex_to_slayout": ([c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_spec_sep_mul": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_spec_sep_wgrad": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_spec_diag_apply": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_spec_diag_wgrad": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_pointwise_chunks": ([c_ll, c_int, c_ll], c_int),
-    "mk_plane_sums": ([c_vp, c_int, c_vp, c_vp, c_ll, c_ll, c_vp], c_int),
-    "mk_instnorm_stats": ([c_vp, c_int, c_vp, c_vp, c_ll, c_ll, c_f, c_vp, c_f, c_vp], c_int),
-    "mk_instnorm_merge": ([c_vp, c_vp, c_vp, c_ll, c_int, c_f, c_vp], c_int),
-    "mk_instnorm_apply": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_instnorm_fused_chunks": ([c_ll, c_int, c_ll, c_int], c_int),
-    "mk_instnorm_fwd_fused": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_f, c_int, c_vp], c_int),
-    "mk_instnorm_bwd_fused": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_instnorm_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_vp, c_vp, c_ll, c_int, c_ll, c_ll, c_int, c_int, c_vp], c_int),
-    "mk_chan_layernorm_chunks": ([c_int, c_ll], c_int),
-    "mk_chan_layernorm_fwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_f, c_vp], c_int),
-    "mk_chan_layernorm_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_chan_layernorm_wgrad": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_bias_gelu_fwd": ([c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_ll, c_vp], c_int),
-    "mk_conv1x1_nn": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_conv1x1_wgrad_workspace": ([c_int, c_int, c_int, c_ll], c_ll),
-    "mk_conv1x1_wgrad": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_conv1x1_wgrad_fuses_bias": ([c_int, c_int, c_int, c_ll], c_int),
-    "mk_conv1x1_wgrad_bias": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_adamw_step": ([c_vp, c_vp, c_vp, c_vp, c_ll, c_vp, c_f, c_f, c_f, c_f, c_f, c_int, c_vp, c_vp], c_int),
-    "mk_adamw_advance": ([c_vp, c_f, c_f, c_vp], c_int),
-    "mk_bias_gelu_bwd": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_ll, c_int, c_ll, c_vp], c_int),
-    "mk_adamw_multi": ([c_vp, c_int, c_vp, c_f, c_f, c_f, c_f, c_f, c_int, c_vp, c_vp], c_int),
-    "mk_instnorm_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_ll, c_int, c_ll, c_f, c_int, c_vp], c_int),
-    "mk_grad_norm_workspace": ([c_vp, c_int], c_ll),
-    "mk_grad_clip_coef": ([c_vp, c_int, c_f, c_vp, c_vp, c_vp], c_int),
-    "mk_grad_norm_workspace_pre": ([c_vp, c_int, c_vp, c_int], c_ll),
-    "mk_grad_clip_coef_pre": ([c_vp, c_int, c_vp, c_int, c_f, c_vp, c_vp, c_vp], c_int),
-    "mk_spec_lp_blocks": ([c_int, c_int], c_ll),
-    "mk_spec_lp_fwd": ([c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_int, c_int, c_f, c_f, c_f, c_vp], c_int),
-    "mk_spec_lp_bwd": ([c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_int, c_int, c_f, c_f, c_f, c_vp], c_int),
-    "mk_crps_chunks": ([c_ll], c_int),
-    "mk_crps": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_f, c_f, c_int, c_vp, c_vp], c_int),
-    "mk_crps_complex": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_f, c_int, c_vp], c_int),
-    "mk_escore_sums_workspace": ([c_int, c_int, c_int, c_ll, c_int, c_int], c_ll),
-    "mk_escore_sums": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_int, c_f, c_vp], c_int),
-    "mk_escore_finish": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_vp], c_int),
-    "mk_escore_grad": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_ll, c_int, c_int, c_f, c_vp], c_int),
-    "mk_mmd_finish": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_f, c_f, c_vp], c_int),
-    "mk_amse_sums": ([c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_amse_grad": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_ens_nll_chunks": ([c_ll], c_int),
-    "mk_ens_nll": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_f, c_int, c_vp], c_int),
-    "mk_metric_chunks": ([c_ll], c_int),
-    "mk_metric_det_sums": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_metric_ens_sums": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_int, c_vp], c_int),
-    "mk_noise_update": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_noise_advance": ([c_vp, c_ll, c_vp], c_int),
-    "mk_noise_update_shard": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                               c_int, c_vp], c_int),
-    "mk_disco_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_disco_bwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_disco_bwd_same": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_disco_runs_shape": ([c_int, c_int, c_int, c_int, c_int, c_vp, c_vp], c_int),
-    "mk_disco_fused_shape": ([c_int, c_int, c_int, c_int, c_vp, c_vp], c_int),
-    "mk_disco_fwd_fused": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_disco_fwd_runs": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_disco_bwd_runs": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_group_mix_supported": ([c_int, c_int], c_int),
-    "mk_group_mix_blocks": ([c_ll, c_int, c_int], c_int),
-    "mk_group_mix": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_group_mix_wgrad": ([c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_resample_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_resample_bwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp], c_int),
-    "mk_quad_lp_chunks": ([c_ll], c_int),
-    "mk_quad_lp_fwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_int, c_f, c_vp], c_int),
-    "mk_quad_lp_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_ll, c_int, c_f, c_vp], c_int),
-    "mk_prep_chunks": ([c_ll], c_int),
-    "mk_prep_stats": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_ll,
-                       c_vp], c_int),
-    "mk_prep_assemble": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
-                          c_int, c_ll, c_vp], c_int),
-    "mk_prep_finish": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_prep_bwd_sums": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int,
-                          c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_prep_bwd_apply": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int,
-                           c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_prep_finish_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_welford_update": ([c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_power_spectrum": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                           c_int, c_vp], c_int),
-    "mk_zonal_welford": ([c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                          c_vp], c_int),
-    "mk_cmix_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f, c_ll,
-                     c_vp], c_int),
-    "mk_cmix_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_f, c_f,
-                     c_ll, c_vp], c_int),
-    "mk_nonneg_fwd": ([c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_nonneg_bwd": ([c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_f, c_f, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_si_assemble": ([c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, C.c_double, c_int, c_int, c_int, c_int, c_int,
-                        c_int, c_ll, c_vp], c_int),
-    "mk_si_step": ([c_vp, c_ll, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_f, c_f, c_f, c_f, c_f, c_int,
-                    c_int, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-    "mk_si_step_bwd": ([c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_f, c_f, c_f, c_int, c_int, c_int, c_int, c_ll, c_vp], c_int),
-}
+with open(HEADER) as _f:
+    CONSTS, STRUCTS, _SIGS = parse_header(_f.read())
 
-EXPORTS = sorted(list(_SIGS) + ["mk_last_error"])
+MK_F32, MK_BF16, MK_FFT_SEG_MAX = (CONSTS[k] for k in ("MK_F32", "MK_BF16", "MK_FFT_SEG_MAX"))
+TRI_NONE, TRI_ROW_GE, TRI_K_GE, TRI_ROW_LE, TRI_K_LE = (CONSTS["MK_TRI_" + k] for k in ("NONE", "ROW_GE", "K_GE", "ROW_LE", "K_LE"))
+MkGemm, MkFftSeg, MkAdamTensor = (STRUCTS[k] for k in ("MkGemm", "MkFftSeg", "MkAdamTensor"))
+EXPORTS = sorted(_SIGS)
 
 _lib = None
 
@@ -189,8 +152,6 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = args
             fn.restype = res
-        L.mk_last_error.argtypes = []
-        L.mk_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 

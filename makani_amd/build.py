@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+from ._lib import HEADER
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmakani_amd.so")
@@ -31,7 +33,7 @@ def _stale(obj, src):
     if not os.path.exists(obj):
         return True
     t = os.path.getmtime(obj)
-    deps = [src] + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "makani_amd.h")]
+    deps = [src] + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -31,14 +31,15 @@ import torch
 import torch.nn as nn
 
 from . import comm as _comm
-from ._lib import check, device_guard, dtype_code, lib, need_gpu, prep, ptr, stream
+from ._lib import CONSTS, check, device_guard, dtype_code, lib, need_gpu, prep, ptr, stream
 from .ensemble import check_forecast_dims, check_weight_dims, ensemble_active, ensemble_size_check, flatten_and_split
 from .losses import CRPSLoss, GridQuadrature, grid_to_quadrature_rule
 
-SUM_L1, SUM_L2, SUM_XY, SUM_XX, SUM_YY = 1, 2, 4, 8, 16          # MK_METRIC_* of include/makani_amd.h: bit k selects [..., k]
-SUM_ALL = 31
+# MK_METRIC_* of include/makani_amd.h: bit k selects [..., k]
+SUM_L1, SUM_L2, SUM_XY, SUM_XX, SUM_YY = (CONSTS["MK_METRIC_" + k] for k in ("L1", "L2", "XY", "XX", "YY"))
+SUM_ALL = SUM_L1 | SUM_L2 | SUM_XY | SUM_XX | SUM_YY
 SUM_ACC = SUM_XY | SUM_XX | SUM_YY
-ENS_SKILL, ENS_SPREAD, ENS_HIST = 1, 2, 4
+ENS_SKILL, ENS_SPREAD, ENS_HIST = (CONSTS["MK_METRIC_" + k] for k in ("SKILL", "SPREAD", "HIST"))
 
 
 class LossType(object):

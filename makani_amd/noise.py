@@ -29,7 +29,7 @@ import torch.nn as nn
 from . import _lib, comm
 from .sht import InverseRealSHT
 
-MODE_WHITE, MODE_AR, MODE_REPLACE = 0, 1, 2
+MODE_WHITE, MODE_AR, MODE_REPLACE = (_lib.CONSTS["MK_NOISE_" + k] for k in ("WHITE", "AR", "REPLACE"))
 
 
 class BaseNoiseS2(nn.Module):

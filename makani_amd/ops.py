@@ -1619,8 +1619,7 @@ class DistInstanceNormFn(torch.autograd.Function):
 
 
 # ---- physical output constraints (csrc/constraints.hip) ---------------------------------------------------------------------
-CMIX_ROWS, CMIX_LEVELS = 32, 16          # MK_CMIX_ROWS, MK_CMIX_LEVELS of include/makani_amd.h
-CMIX_RESID, CMIX_Q_ROUNDTRIP = 1, 2
+CMIX_ROWS, CMIX_LEVELS, CMIX_RESID, CMIX_Q_ROUNDTRIP = (_lib.CONSTS["MK_CMIX_" + k] for k in ("ROWS", "LEVELS", "RESID", "Q_ROUNDTRIP"))
 
 
 @dataclass

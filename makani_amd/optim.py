@@ -6,7 +6,6 @@ reduction of every large gradient with a reduce-scatter instead of an all-reduce
 all-reduce); ``FusedAdamW`` then keeps ``exp_avg`` / ``exp_avg_sq`` only for this rank's 1/N slice of such a parameter,
 updates that slice (1/N of the 28 B per element the update streams through HBM) and all-gathers the parameter in place.
 With N = 8 the optimizer pass of the benchmark model goes from 16 GB of HBM traffic per rank to 2 GB + the gathered 2.3 GB."""
-import ctypes as C
 
 import torch
 import torch.distributed as dist
@@ -31,16 +30,14 @@ def _k_adamw(pr, gr, m, v, scale, lr, b1, b2, eps, wd, sdev):
 
 
 def _descs(ts):
-    arr = (MkAdamTensor * max(1, len(ts)))(*[MkAdamTensor(None, t.data_ptr(), None, None, t.numel(), None, None, 0, 0, 0) for t in ts])
-    return C.cast(arr, C.c_void_p), arr
+    return (MkAdamTensor * max(1, len(ts)))(*[MkAdamTensor(None, t.data_ptr(), None, None, t.numel(), None, None, 0, 0, 0) for t in ts])
 
 
 def _k_sumsq_clip(grads, max_grad_norm, pre=()):
     """(2,) device tensor [min(1, max_norm / (||g|| + 1e-6)), ||g||] over a list of flat fp32 tensors; ``pre``: buffers of partial
     sums of squares that stand in for gradients not in ``grads`` (``ops.grad_ssq_lookup``)"""
     dev = (grads[0] if grads else pre[0]).device
-    ga, _keep_g = _descs(grads)
-    pa, _keep_p = _descs(pre)
+    ga, pa = _descs(grads), _descs(pre)
     nws = lib().mk_grad_norm_workspace_pre(ga, len(grads), pa, len(pre))
     ws = torch.empty((nws,), dtype=torch.float32, device=dev)
     out = torch.empty((2,), dtype=torch.float32, device=dev)
@@ -281,7 +278,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 arr = (MkAdamTensor * len(descs))(*descs)
                 from .ops import _timed
                 with _timed("adamw_multi", nbytes=28.0 * sum(d.n for d in descs)):
-                    check(lib().mk_adamw_multi(C.cast(arr, C.c_void_p), len(descs), ptr(scale), group["lr"], b1, b2, group["eps"],
+                    check(lib().mk_adamw_multi(arr, len(descs), ptr(scale), group["lr"], b1, b2, group["eps"],
                                                group["weight_decay"], 0, ptr(sdev), stream()), "mk_adamw_multi")
             for p in shadowed:               # valid for exactly this version (and storage) of the parameter
                 p._mk_shadow_version = p._version

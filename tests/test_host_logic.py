@@ -1,4 +1,4 @@
-"""CPU tests: the C-ABI library loads and exports every symbol the header declares, the host-side
+"""CPU tests: the C-ABI library validates its arguments on the host (the ABI itself: tests/test_abi.py), the host-side
 precompute agrees with the oracle, the drop-in modules keep the reference's interface
 (constructor, attributes, state_dict, error behaviour) and refuse to run without the HIP path."""
 import ctypes
@@ -17,29 +17,6 @@ SFNO_GOLDEN = ["sfno_tiny_64x128.npz", "sfno_small_37x72.npz", "sfno_s2norm_resa
                "sfno_options_b_24x48.npz", "sfno_layernorm_24x48.npz"]
 
 from conftest import ROOT, load_golden
-
-
-def test_library_exports_every_declared_symbol():
-    from makani_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    L = ctypes.CDLL(_lib.LIB_PATH)
-    header = open(os.path.join(ROOT, "include", "makani_amd.h")).read()
-    declared = set(re.findall(r"\b(mk_[a-z0-9_]+)\s*\(", header))
-    assert declared, "no declarations parsed"
-    for sym in declared:
-        assert hasattr(L, sym), f"{sym} declared in include/makani_amd.h but not exported"
-    assert set(_lib.EXPORTS) == declared, (set(_lib.EXPORTS) ^ declared)
-    assert _lib.lib().mk_version() >= 100
-
-
-def test_gemm_descriptor_matches_header_layout():
-    from makani_amd._lib import MkGemm
-    header = open(os.path.join(ROOT, "include", "makani_amd.h")).read()
-    body = header[header.index("typedef struct MkGemm {"):header.index("} MkGemm;")]
-    names = re.findall(r"\b([a-zA-Z_]+)\s*(?=[,;])", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
-    names = [n for n in names if n not in ("float", "int", "long", "const")]
-    assert names == [f for f, _ in MkGemm._fields_]
 
 
 def test_argument_validation_without_gpu():

@@ -93,9 +93,3 @@ def test_errors_on_cpu_tensors():
         ma.SpectralAMSELoss(**KW)(f4, o)
     with pytest.raises(NotImplementedError):
         ma.GaussianMMDLoss(beta=0.5, **KW)
-
-
-def test_entry_points_are_declared():
-    from makani_amd import _lib
-    for name in ("mk_amse_sums", "mk_amse_grad", "mk_ens_nll", "mk_ens_nll_chunks", "mk_mmd_finish"):
-        assert name in _lib.EXPORTS

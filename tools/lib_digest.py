@@ -206,7 +206,7 @@ def optim():
     emit("adamw_step", st, p, m, v)
     p2, m2, v2 = rnd(n), rnd(n, scale=0.1), rnd(n, pos=True)
     desc = (_lib.MkAdamTensor * 1)(_lib.MkAdamTensor(p2.data_ptr(), g.data_ptr(), m2.data_ptr(), v2.data_ptr(), n, None, None, 0, 0, 0))
-    check(lib().mk_adamw_multi(C.cast(desc, C.c_void_p), 1, None, 1e-3, 0.9, 0.999, 1e-8, 0.01, 0, ptr(st), stream()))
+    check(lib().mk_adamw_multi(desc, 1, None, 1e-3, 0.9, 0.999, 1e-8, 0.01, 0, ptr(st), stream()))
     emit("adamw_multi", p2, m2, v2)
 
 
