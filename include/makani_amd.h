@@ -257,6 +257,14 @@ int mk_instnorm_fwd_fused(const void* x, void* y, int dtype, float* stats, const
 int mk_instnorm_bwd_fused(const void* x, const void* gy, void* gx, int dtype, const float* stats, const float* gamma,
                           const float* beta, const float* pre_bias, float* sums, void* slots, void* depart, long long planes,
                           int channels, long long hw, int fuse_gelu, void* stream);
+/* The statistics of mk_instnorm_fwd_fused WITHOUT its apply phase, for a consumer that normalises the plane where it reads it
+ * (mk_conv1x1_nn_rnorm): stats (planes, 2) = (mean, rstd), bit for bit what mk_instnorm_fwd_fused writes for the same input, and
+ * coef (planes rounded up to a multiple of 8, 2) = (sc, sh) = (rstd gamma, beta - mean rstd gamma), the two numbers of the apply
+ * y = bf16(pre(x) sc + sh); rows past `planes` are not written.  ws: planes * mk_instnorm_fused_chunks(hw, dtype, planes, 0) * 2
+ * floats, no initial state.  Two launches ordered by the stream: partial sums per chunk (plain stores), then one block per
+ * plane; no hand-over between workgroups. */
+int mk_instnorm_stats_fused(const void* x, int dtype, float* stats, float* coef, float* ws, const float* gamma, const float* beta,
+                            const float* pre_bias, long long planes, int channels, long long hw, float eps, void* stream);
 /* y = gelu(x + bias[c])  — the bias+activation of the 1x1 convolutions in MLP / EncoderDecoder
  * (makani/models/common/layers.py:603-643,768-823).  bias may be NULL (plain GELU).
  * Backward: gx = gy * gelu'(x + bias[c]); optional sums (2, planes): sums[0][p] = sum gx (bias grad). */
@@ -337,6 +345,16 @@ int mk_spec_diag_wgrad(const float* x, const float* gy, float* gw_c64, int L, in
  *       takes the plane sums with mk_plane_sums. */
 int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, const float* bias, const void* R, const void* G,
                   int M, int K, int lda, int B, long long N, int act, void* stream);
+/* Y = A X (+ bias) + norm(R [+ pre_bias]): mk_conv1x1_nn whose residual operand R is the INPUT of an instance norm that nobody
+ * else consumes.  coef (B * channels, 2): (sc, sh) per plane of R from mk_instnorm_stats_fused; pre_bias (channels) or NULL: the
+ * constant folded in front of the norm; channels == M.  The epilogue adds bf16(bf16(R + pre_bias[c]) sc + sh), bit for bit the
+ * tensor mk_instnorm_fwd_fused would have written, so Y equals the two-step result.  Ypre, G and act must be NULL / 0.  Served
+ * exactly where mk_conv1x1_nn_rnorm_supported returns 1 (where mk_conv1x1_nn runs its two-group weight-stationary kernel for a
+ * call with R); any other shape is an error. */
+int mk_conv1x1_nn_rnorm(const void* A, const void* X, void* Y, void* Ypre, const float* bias, const void* R, const void* G,
+                        int M, int K, int lda, int B, long long N, int act, const float* coef, const float* pre_bias, int channels,
+                        void* stream);
+int mk_conv1x1_nn_rnorm_supported(int M, int K, int lda, int B, long long N);
 long long mk_conv1x1_wgrad_workspace(int M, int K, int B, long long N);
 int mk_conv1x1_wgrad(const void* G, const void* X, float* dW, float* part, int M, int K, int B, long long N,
                      int accumulate, void* stream);

@@ -59,6 +59,11 @@ struct ConvNN {
     int act;
     int nt;              // output stores with the streaming (nt) cache policy: set by the launcher for outputs that fit the memory-side cache
 };
+// mk_conv1x1_nn_rnorm: R is the INPUT of an instance norm, normalised where the epilogue adds it (conv_nn_astat2_kernel<false, true, true>)
+struct ConvNNRnorm : ConvNN {
+    const float* coef;   // (B * M, 2): (sc, sh) per plane of R = (rstd gamma, beta - mean rstd gamma), from mk_instnorm_stats_fused
+    const float* pb;     // optional (M): constant added to R (rounded to bf16) in front of the norm
+};
 
 __device__ __forceinline__ uint4 ld16(const u16* p) { return *reinterpret_cast<const uint4*>(p); }
 // Output stores.  Measured (gpurun_out/r07l, same box): with the streaming (nt) policy the K = 384 / 768 kernels are 7-15 % faster at
@@ -1100,9 +1105,16 @@ __global__ __launch_bounds__(256, (KS < 24 && !EPI_LOADS) ? 2 : 1) void conv_nn_
 // LDS: ring 96 / 64 KB + 24 KB staging image per group + (epilogue operand) 24 KB per group = 144 / 160 KB.
 // Fragment reads: ds_read_b64_tr_b16 on [k][pixel] rows of 128 B; the 16-byte chunk index of a row is XOR-swizzled with
 // ((k >> 1) & 1) << 2 (as above) and (k >> 3 & 1) << 1 (the two 16-lane groups of a half-wave read k-blocks 8 rows apart).
-template <bool PRE, bool EPI_LOADS>
-__global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const ConvNN p, int slabs, long long tilesN) {
+// RNORM (PRE = false, EPI_LOADS = true, operand R only): R is the input z of an instance norm whose output is consumed here and
+// nowhere else; the epilogue adds bf16(bf16(z + pb[c]) sc + sh) — the value in_fwd_fused (csrc/pointwise.hip) would have stored,
+// same contraction, same conversion — instead of R.  A wave reads back the same 48 channels in every tile (3 rounds x 2 halves x 8
+// rows): lane j < 48 loads (sc, sh, pb) of the j-th of them in the prologue (three registers, vector loads before any DMA piece is
+// in flight) and every half-round fetches its row's three numbers from that lane with ds_bpermute_b32 — the LDS crossbar, no LDS
+// storage, lgkmcnt: the counted vmcnt waits see no new instruction.  The other instantiations compile to what they were.
+template <bool PRE, bool EPI_LOADS, bool RNORM = false>
+__global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const std::conditional_t<RNORM, ConvNNRnorm, ConvNN> p, int slabs, long long tilesN) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(!RNORM || (!PRE && EPI_LOADS), "the normalising operand is R of the plain epilogue");
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
     constexpr int KS = 12;                              // k32-steps: K = 384
     constexpr int KCH = 128, NCH = 3, K4 = 4;           // chunk: 128 input channels = 4 k32-steps; 3 chunks per pixel tile
@@ -1168,12 +1180,23 @@ __global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const ConvNN p, int
         const int mrow = m_base + ct * 16 + c16;
         bvr[ct] = (p.bias && mrow < p.M) ? p.bias[mrow] : 0.f;
     }
+    // RNORM: lane j < 48 keeps the norm coefficients of channel row j = (3 u2 + ct) * 8 + r of this wave's read-back order (round ct,
+    // half u2, row r); rows past M: the last row (their stores are dropped); without pb -0.0f (z + -0.0f is z for every z)
+    float cf_sc = 0.f, cf_sh = 0.f, cf_pb = -0.0f;
+    if constexpr (RNORM) {
+        const int j = min(lane, 47), hr = j >> 3;
+        const int mrow = min(slab * 384 + (wave >> 2) * 192 + (((wave & 3) >> 1) + 2 * (hr / 3)) * 48 + (hr % 3) * 16 + (wave & 1) * 8 + (j & 7), p.M - 1);
+        const float2 c2 = *reinterpret_cast<const float2*>(p.coef + ((long long)blockIdx.y * p.M + mrow) * 2);
+        cf_sc = c2.x, cf_sh = c2.y;
+        if (p.pb) cf_pb = p.pb[mrow];
+    }
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {                   // wait for the weights here, before any DMA piece is in flight
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(wf[ct][ks]));
         asm volatile("" : "+v"(bvr[ct]));
     }
+    if constexpr (RNORM) asm volatile("" : "+v"(cf_sc), "+v"(cf_sh), "+v"(cf_pb));
 
     // ---- DMA of the activation chunks: wave w issues pieces 2 w, 2 w + 1 (rows 16 w .. 16 w + 15 of the chunk) ----
     const unsigned lds0 = lds_addr(smem) + (unsigned)wave * (NP * 1024);
@@ -1291,6 +1314,37 @@ __global__ __launch_bounds__(512) void conv_nn_astat2_kernel(const ConvNN p, int
         const unsigned cn0b = (unsigned)(pfirst + ts * pstride) * 128u;           // first pixel of the tile, in bytes (32-bit: M N 2 < 2^31)
         typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
         const int tg = (wg << 6) | lane_here();         // thread inside the group
+        if constexpr (RNORM) {                          // plain epilogue, R normalised where it is added
+#pragma unroll
+            for (int u2 = 0; u2 < 2; ++u2) {
+                const int idx = tg + 256 * u2;
+                const int row = idx >> 3, ch = idx & 7;
+                const int srow = ct * 64 + row;
+                const int grow = (row >> 4) * 48 + ct * 16 + (row & 15);
+                const int m = slab * 384 + grp * 192 + grow;
+                const unsigned nb = cn0b + (unsigned)ch * 16u;
+                const bool live = m < p.M && nb < nbytes;
+                const unsigned voff = live ? (unsigned)m * nbytes + nb : 0xC0000000u;
+                const uint4 raw = *reinterpret_cast<const uint4*>(stgG + srow * 128 + ((ch ^ ((srow >> 1) & 7)) * 16));
+                const uint4 ev = *reinterpret_cast<const uint4*>(ebufG + grow * 128 + ch * 16);
+                const int src = (((3 * u2 + ct) * 8) + (row & 7)) * 4;          // lane that holds this row's coefficients, as a byte address
+                const float rsc = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(cf_sc)));
+                const float rsh = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(cf_sh)));
+                const float rpb = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(cf_pb)));
+                const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+                const uint32_t rw[4] = {ev.x, ev.y, ev.z, ev.w};
+                uint32_t o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {           // in_fwd_fused's apply: pre<u16>(z, pb) * sc + sh, stored through pack_bf16x2
+                    const uint32_t zb = pack_bf16x2(__uint_as_float(rw[e] << 16) + rpb, __uint_as_float(rw[e] & 0xffff0000u) + rpb);
+                    const uint32_t yb = pack_bf16x2(__uint_as_float(zb << 16) * rsc + rsh, __uint_as_float(zb & 0xffff0000u) * rsc + rsh);
+                    o[e] = pack_bf16x2(__uint_as_float(w[e] << 16) + __uint_as_float(yb << 16),
+                                       __uint_as_float(w[e] & 0xffff0000u) + __uint_as_float(yb & 0xffff0000u));
+                }
+                MK_BUF_ST16((u32x4_t{o[0], o[1], o[2], o[3]}), rsY, voff, nt_st);
+            }
+            return;
+        }
 #pragma unroll
         for (int u2 = 0; u2 < 2; ++u2) {
             const int idx = tg + 256 * u2;
@@ -1951,6 +2005,42 @@ extern "C" int mk_conv1x1_nn(const void* A, const void* X, void* Y, void* Ypre, 
     }
     }
     return mk_check_launch("mk_conv1x1_nn");
+}
+
+// Y = A X + norm(R [+ pre_bias]): the skip GEMM of a block whose other branch ends in an instance norm.  R is the norm's INPUT;
+// coef (B * channels, 2) holds (sc, sh) per plane (mk_instnorm_stats_fused), pre_bias (channels) or null the constant folded in
+// front of the norm.  The value added is bit for bit what mk_instnorm_fwd_fused would have written.  Only where
+// mk_conv1x1_nn_rnorm_supported says so (the two-group weight-stationary kernel): anything else is an error, not another kernel.
+extern "C" int mk_conv1x1_nn_rnorm_supported(int M, int K, int lda, int B, long long N) {
+    static const int astat2_env = env_int("MAKANI_AMD_ASTAT2");
+    return conv_nn_rnorm_supported(M, K, lda, B, N, astat2_env) ? 1 : 0;
+}
+
+extern "C" int mk_conv1x1_nn_rnorm(const void* A, const void* X, void* Y, void* Ypre, const float* bias, const void* R,
+                                   const void* G, int M, int K, int lda, int B, long long N, int act, const float* coef,
+                                   const float* pre_bias, int channels, void* stream) {
+    MK_REQUIRE(A && X && Y && R && coef, "conv1x1_nn_rnorm: null pointer");
+    MK_REQUIRE(!Ypre && !G && !act, "conv1x1_nn_rnorm: the normalising operand comes with the plain epilogue only");
+    MK_REQUIRE(M > 0 && K > 0 && B > 0 && N > 0, "conv1x1_nn_rnorm: bad shape M=%d K=%d B=%d N=%lld", M, K, B, N);
+    MK_REQUIRE(channels == M, "conv1x1_nn_rnorm: the norm has %d channels, the output %d", channels, M);
+    MK_REQUIRE((lda % 8) == 0 && lda >= K, "conv1x1_nn_rnorm: lda=%d must be a multiple of 8 and >= K=%d", lda, K);
+    MK_REQUIRE((N % 8) == 0, "conv1x1_nn_rnorm: pixel count %lld must be a multiple of 8", N);
+    MK_REQUIRE((((uintptr_t)A | (uintptr_t)X | (uintptr_t)R) & 15) == 0, "conv1x1_nn_rnorm: operands must be 16-byte aligned");
+    MK_REQUIRE(((uintptr_t)coef & 7) == 0 && ((uintptr_t)pre_bias & 3) == 0, "conv1x1_nn_rnorm: coef must be 8-byte, pre_bias 4-byte aligned");
+    MK_REQUIRE(mk_conv1x1_nn_rnorm_supported(M, K, lda, B, N), "conv1x1_nn_rnorm: shape M=%d K=%d B=%d N=%lld is not served", M, K, B, N);
+    static const int nt_env = env_int("MAKANI_AMD_CONV_NT");
+    const long long out_bytes = (long long)B * M * N * 2;
+    const int nt = nt_env == 0 ? 0 : (nt_env == 1 ? 1 : out_bytes <= (256ll << 20));      // as mk_conv1x1_nn
+    ConvNNRnorm p{};
+    static_cast<ConvNN&>(p) = ConvNN{(const u16*)A, (const u16*)X, (u16*)Y, nullptr, bias, (const u16*)R, nullptr, M, K, lda, B, N, 0, nt};
+    p.coef = coef;
+    p.pb = pre_bias;
+    const int slabs = (M + 383) / 384;
+    const long long tn64 = (N + 63) / 64;
+    const long long streams = tn64 < 256 / slabs ? tn64 : 256 / slabs;
+    const dim3 grid((unsigned)(streams * slabs), (unsigned)B), blk(512);
+    hipLaunchKernelGGL((conv_nn_astat2_kernel<false, true, true>), grid, blk, 0, (hipStream_t)stream, p, slabs, tn64);
+    return mk_check_launch("mk_conv1x1_nn_rnorm");
 }
 
 // ---- host-side plan of the weight gradient -------------------------------------------------

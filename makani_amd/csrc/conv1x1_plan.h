@@ -28,6 +28,12 @@ inline ConvNnKernel conv_nn_plan(int M, int K, int lda, int B, long long N, bool
     return ConvNnKernel::tile;
 }
 
+// mk_conv1x1_nn_rnorm (the skip GEMM that normalises its residual operand where it adds it) exists on the two-group kernel only:
+// true exactly where the plain call with a residual operand plans it.
+inline bool conv_nn_rnorm_supported(int M, int K, int lda, int B, long long N, int astat2_env) {
+    return conv_nn_plan(M, K, lda, B, N, /*pre=*/false, /*has_r=*/true, /*has_g=*/false, astat2_env) == ConvNnKernel::astat2;
+}
+
 // Tile height of the ring kernel (output channels per tile; the tile is 256 pixels wide): 256 where M is made of whole 256-row tiles
 // or is large, else 192 — and ONE 384-row tile where that would be two of 192 under a long contraction (384 <- 768, the MLP's second
 // layer and the data gradient of its first).  Per 256 pixels the two 192-row tiles ingest 2 x (192 x K weights + K x 256 activations),

@@ -614,6 +614,102 @@ __global__ __launch_bounds__(NT) void in_fwd_fused(const T* __restrict__ x, T* _
     }
 }
 
+// ---- statistics only (the apply happens in the consumer: mk_conv1x1_nn_rnorm adds the normalised plane in its epilogue) ----
+// in_stats_fused: the load / pivot / partial-sum phase of in_fwd_fused<T, false>, same chunking, same arithmetic; thread 0 leaves
+// the block's pair in ws[(plane, chunk)] with a plain store and the block ends — no sentinel, no departure counter, no spin.
+// in_stats_finish (next launch on the stream, one block per plane) sums the plane's pairs in fused_gather's order and writes what
+// in_fwd_fused would have: stats = (mean, rstd), bit for bit, and coef = (sc, sh), the two numbers of its apply phase.
+template <typename T>
+__global__ __launch_bounds__(NT) void in_stats_fused(const T* __restrict__ x, float* __restrict__ ws, int channels, long long hw,
+                                                     int chunks, const float* __restrict__ pre_bias) {
+    constexpr int VEC = VecIO<T>::N;
+    constexpr int FUSED_SLOTS = fused_slots(0);
+    typedef typename VecIO<T>::Raw Raw;
+    __shared__ float red[2 * NT / 64];
+    const long long plane = blockIdx.x / chunks;
+    const int chunk = blockIdx.x % chunks;
+    const int c = (int)(plane % channels);
+    const bool has_pb = pre_bias != nullptr;
+    const float pb = has_pb ? pre_bias[c] : 0.f;
+    const T* xp = x + plane * hw;
+    const long long len = chunk_len(hw, chunks, VEC);
+    const long long c0 = (long long)chunk * len;
+    const long long c1 = min(hw, c0 + len);
+    Raw raw[FUSED_SLOTS];
+#pragma unroll
+    for (int s = 0; s < FUSED_SLOTS; ++s) {
+        const long long e = c0 + ((long long)s * NT + threadIdx.x) * VEC;
+        raw[s] = VecIO<T>::load_raw_nt(xp + (e < c1 ? e : c0));
+    }
+    const float pivot = pre<T>(VecIO<T>::load1(xp), pb, has_pb);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int s = 0; s < FUSED_SLOTS; ++s) {
+        const long long e = c0 + ((long long)s * NT + threadIdx.x) * VEC;
+        if (e < c1) {
+            float v[VEC];
+            VecIO<T>::unpack(raw[s], v);
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) {
+                const float d = pre<T>(v[i], pb, has_pb) - pivot;
+                s1 += d;
+                s2 += d * d;
+            }
+        }
+    }
+    block_reduce2(s1, s2, red);
+    if (threadIdx.x == 0) {
+        ws[2 * (plane * chunks + chunk)] = s1;
+        ws[2 * (plane * chunks + chunk) + 1] = s2;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(NT) void in_stats_finish(const T* __restrict__ x, const float* __restrict__ ws, float* __restrict__ stats,
+                                                      float* __restrict__ coef, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float eps, int channels, long long hw, int chunks,
+                                                      const float* __restrict__ pre_bias) {
+    __shared__ double redd[2 * NT / 64];
+    const long long plane = blockIdx.x;
+    const int c = (int)(plane % channels);
+    const bool has_pb = pre_bias != nullptr;
+    const float pb = has_pb ? pre_bias[c] : 0.f;
+    const float pivot = pre<T>(VecIO<T>::load1(x + plane * hw), pb, has_pb);
+    double a = 0.0, b = 0.0;
+    if ((int)threadIdx.x < chunks) {                     // chunks <= NT
+        a = (double)ws[2 * (plane * chunks + threadIdx.x)];
+        b = (double)ws[2 * (plane * chunks + threadIdx.x) + 1];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_down(a, o, 64);
+        b += __shfl_down(b, o, 64);
+    }
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    if (lane == 0) {
+        redd[2 * w] = a;
+        redd[2 * w + 1] = b;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double t1 = 0.0, t2 = 0.0;
+    for (int i = 0; i < NT / 64; ++i) {
+        t1 += redd[2 * i];
+        t2 += redd[2 * i + 1];
+    }
+    const double m = t1 / (double)hw;
+    double var = t2 / (double)hw - m * m;        // (the lines of in_fwd_fused)
+    if (var < 0.0) var = 0.0;
+    const float mean = (float)((double)pivot + m);
+    const float rstd = (float)(1.0 / sqrt(var + (double)eps));
+    stats[2 * plane] = mean;
+    stats[2 * plane + 1] = rstd;
+    const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    const float sc = rstd * g, sh = bt - mean * rstd * g;
+    coef[2 * plane] = sc;
+    coef[2 * plane + 1] = sh;
+}
+
 // backward in one pass: gx = rstd gamma (ga - S1 / hw - n S2 / hw) with S1 = sum ga, S2 = sum ga n over the plane
 template <typename T, bool GELU>
 __global__ __launch_bounds__(NT) void in_bwd_fused(const T* __restrict__ x, const T* __restrict__ gy, T* __restrict__ gx,
@@ -1096,6 +1192,32 @@ extern "C" int mk_instnorm_fwd_fused(const void* x, void* y, int dtype, float* s
     }
 #undef IN_FF
     return mk_check_launch("mk_instnorm_fwd_fused");
+}
+
+// Statistics of the one-pass forward without its apply phase: stats (planes, 2) = (mean, rstd), bit for bit what
+// mk_instnorm_fwd_fused writes for the same input, and coef (planes rounded up to a multiple of 8, 2) = (sc, sh) =
+// (rstd gamma, beta - mean rstd gamma) for a consumer that normalises the plane itself (mk_conv1x1_nn_rnorm; rows past `planes` are
+// not written).  ws: planes * mk_instnorm_fused_chunks(hw, dtype, planes, 0) * 2 floats, no initial state.  Two launches, ordered
+// by the stream; no hand-over between workgroups.
+extern "C" int mk_instnorm_stats_fused(const void* x, int dtype, float* stats, float* coef, float* ws, const float* gamma,
+                                       const float* beta, const float* pre_bias, long long planes, int channels, long long hw, float eps,
+                                       void* stream) {
+    int rc = check_common(x, planes, hw, dtype, "instnorm_stats_fused");
+    if (rc) return rc;
+    const int ch = mk_instnorm_fused_chunks(hw, dtype, planes, 0);
+    MK_REQUIRE(ch > 0, "instnorm_stats_fused: plane shape not served (hw = %lld)", hw);
+    MK_REQUIRE(stats && coef && ws && channels > 0, "instnorm_stats_fused: bad args");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g((unsigned)(planes * ch)), gp((unsigned)planes);
+#define IN_SF(T)                                                                                                                    \
+    do {                                                                                                                            \
+        hipLaunchKernelGGL((in_stats_fused<T>), g, dim3(NT), 0, s, (const T*)x, ws, channels, hw, ch, pre_bias);                    \
+        hipLaunchKernelGGL((in_stats_finish<T>), gp, dim3(NT), 0, s, (const T*)x, ws, stats, coef, gamma, beta, eps, channels, hw, \
+                           ch, pre_bias);                                                                                           \
+    } while (0)
+    if (dtype == MK_F32) IN_SF(float); else IN_SF(u16);
+#undef IN_SF
+    return mk_check_launch("mk_instnorm_stats_fused");
 }
 
 extern "C" int mk_instnorm_bwd_fused(const void* x, const void* gy, void* gx, int dtype, const float* stats, const float* gamma,

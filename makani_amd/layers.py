@@ -73,6 +73,19 @@ class PointwiseConv(nn.Module):
         return y
 
 
+def skip_norm_foldable(conv: PointwiseConv, norm, residual, z) -> bool:
+    """``conv(residual) + norm(z)`` can run as one statistics pass and one GEMM (``ops.SkipNormFn``): plain instance norm, bias-free
+    convolution, the bf16 HIP path, and a shape the library serves that way."""
+    if type(norm) is not InstanceNorm2d or conv.bias is not None or not hip_conv_eligible(residual):
+        return False
+    return ops.skip_norm_fold_supported(residual, conv.weight, z)
+
+
+def skip_norm(conv: PointwiseConv, norm, residual, z, pre_bias=None):
+    """conv(residual) + norm(z [+ pre_bias]) without materialising the norm's output (see ``skip_norm_foldable``)"""
+    return ops.SkipNormFn.apply(residual.to(torch.bfloat16), conv.weight, z, norm.weight, norm.bias, norm.eps, pre_bias)
+
+
 class _Act(nn.Module):
     """placeholder keeping the reference's Sequential indices; GELU is fused into the previous op."""
 

@@ -1014,6 +1014,30 @@ def _fused_norm_chunks(x, planes, hw, quad, kind):
     return int(lib().mk_instnorm_fused_chunks(hw, dtype_code(x), planes, kind))
 
 
+def _instnorm_bwd(x, gy, stats, g, b, pb, quad, quad_sum, fuse_gelu):
+    """input gradient of the instance norm and the (2, planes) per-plane sums its gamma / beta gradients are made of"""
+    B, Cc, H, W = x.shape
+    planes, hw = B * Cc, H * W
+    gy = gy.contiguous()
+    if gy.dtype != x.dtype:
+        gy = gy.to(x.dtype)
+    gx = torch.empty_like(x)
+    sums = torch.empty((2, planes), dtype=torch.float32, device=x.device)
+    ch = _fused_norm_chunks(x, planes, hw, quad, 2 if fuse_gelu else 1)
+    if ch:
+        slots, depart = _fused_sync(planes * ch, planes, x.device)
+        with _timed(f"instnorm_bwd{'_gelu' if fuse_gelu else ''}_n{hw}", nbytes=3.0 * x.numel() * x.element_size()):
+            check(lib().mk_instnorm_bwd_fused(ptr(x), ptr(gy), ptr(gx), dtype_code(x), ptr(stats), ptr(g), ptr(b), ptr(pb), ptr(sums),
+                                              ptr(slots), ptr(depart), planes, Cc, hw, 1 if fuse_gelu else 0, stream()), "instnorm_bwd_fused")
+    else:
+        ws = _ws(planes, hw, x.dtype, x.device)
+        with _timed(f"instnorm_bwd{'_gelu' if fuse_gelu else ''}_n{hw}", nbytes=5.0 * x.numel() * x.element_size()):
+            check(lib().mk_instnorm_bwd(ptr(x), ptr(gy), ptr(gx), dtype_code(x), ptr(stats), ptr(g), ptr(b), ptr(pb), ptr(quad),
+                                        quad_sum, ptr(sums), ptr(ws), planes, Cc, hw, hw, 0, 1 if fuse_gelu else 0,
+                                        stream()), "instnorm_bwd")
+    return gx, sums
+
+
 class InstanceNormFn(torch.autograd.Function):
     """nn.InstanceNorm2d(affine) (+ fused exact GELU); fp32 statistics, io in the input dtype.
     ``pre_bias`` (C,) folds a per-channel constant added right in front of the norm (the bias of the MLP's output
@@ -1051,25 +1075,8 @@ class InstanceNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, stats, g, b, pb, quad = ctx.saved_tensors
-        B, Cc, H, W = x.shape
-        planes, hw = B * Cc, H * W
-        gy = gy.contiguous()
-        if gy.dtype != x.dtype:
-            gy = gy.to(x.dtype)
-        gx = torch.empty_like(x)
-        sums = torch.empty((2, planes), dtype=torch.float32, device=x.device)
-        ch = _fused_norm_chunks(x, planes, hw, quad, 2 if ctx.fuse_gelu else 1)
-        if ch:
-            slots, depart = _fused_sync(planes * ch, planes, x.device)
-            with _timed(f"instnorm_bwd{'_gelu' if ctx.fuse_gelu else ''}_n{hw}", nbytes=3.0 * x.numel() * x.element_size()):
-                check(lib().mk_instnorm_bwd_fused(ptr(x), ptr(gy), ptr(gx), dtype_code(x), ptr(stats), ptr(g), ptr(b), ptr(pb), ptr(sums),
-                                                  ptr(slots), ptr(depart), planes, Cc, hw, 1 if ctx.fuse_gelu else 0, stream()), "instnorm_bwd_fused")
-        else:
-            ws = _ws(planes, hw, x.dtype, x.device)
-            with _timed(f"instnorm_bwd{'_gelu' if ctx.fuse_gelu else ''}_n{hw}", nbytes=5.0 * x.numel() * x.element_size()):
-                check(lib().mk_instnorm_bwd(ptr(x), ptr(gy), ptr(gx), dtype_code(x), ptr(stats), ptr(g), ptr(b), ptr(pb), ptr(quad),
-                                            ctx.quad_sum, ptr(sums), ptr(ws), planes, Cc, hw, hw, 0, 1 if ctx.fuse_gelu else 0,
-                                            stream()), "instnorm_bwd")
+        B, Cc = x.shape[:2]
+        gx, sums = _instnorm_bwd(x, gy, stats, g, b, pb, quad, ctx.quad_sum, ctx.fuse_gelu)
         s = _batch_sum(sums, B, Cc)
         gpb = torch.zeros_like(pb) if (pb is not None and ctx.needs_input_grad[5]) else None
         return gx, (s[1] if g is not None else None), (s[0] if b is not None else None), None, None, gpb, None, None
@@ -1260,6 +1267,74 @@ class Conv1x1Fn(torch.autograd.Function):
         if ctx.has_res and ctx.needs_input_grad[3]:
             gr = gy
         return gx, gw, gb, gr
+
+
+def skip_norm_fold_supported(res: torch.Tensor, weight: torch.Tensor, z: torch.Tensor) -> bool:
+    """``SkipNormFn`` serves this call: bf16 planes, the one-pass norm on (MAKANI_AMD_NORM_FUSED), the skip GEMM planned on the
+    two-group weight-stationary kernel (full grids of 384 <- 384; shard-sized grids plan the ring kernel and keep the two-step
+    path), and MAKANI_AMD_NORM1_FOLD not 0 (the A/B switch)."""
+    if os.environ.get("MAKANI_AMD_NORM1_FOLD", "1") == "0":
+        return False
+    if not (res.is_cuda and z.is_cuda and res.dim() == 4 and z.dim() == 4 and z.dtype == torch.bfloat16):
+        return False
+    B, K, H, W = res.shape
+    M = weight.shape[0]
+    if weight.shape[1] != K or tuple(z.shape) != (B, M, H, W) or (H * W) % 8:
+        return False
+    if not lib().mk_conv1x1_nn_rnorm_supported(M, K, round8(K), B, H * W):
+        return False
+    return _fused_norm_chunks(z, B * M, H * W, None, 0) > 0
+
+
+class SkipNormFn(torch.autograd.Function):
+    """out = W res + InstanceNorm(z [+ pre_bias]) on NCHW bf16: the tail of a block.  Forward: the norm's statistics
+    (mk_instnorm_stats_fused: a read-only pass over z), then the skip GEMM, whose epilogue normalises z where it adds it
+    (mk_conv1x1_nn_rnorm) — the norm's output is never materialised.  Bit for bit ``Conv1x1Fn(res, W, None, InstanceNormFn(z))``,
+    forward and backward; the backward runs that pair's kernels on that pair's inputs."""
+
+    @staticmethod
+    def forward(ctx, res, weight, z, gamma, beta, eps, pre_bias):
+        res, z = res.contiguous(), z.contiguous()
+        B, M, H, W = z.shape
+        K = weight.shape[1]
+        planes, hw = B * M, H * W
+        g = gamma.float().contiguous() if gamma is not None else None
+        b = beta.float().contiguous() if beta is not None else None
+        pb = pre_bias.float().contiguous() if pre_bias is not None else None
+        ch = _fused_norm_chunks(z, planes, hw, None, 0)
+        if not ch:
+            raise RuntimeError("SkipNormFn: the one-pass instance norm does not serve this plane shape")
+        stats = torch.empty((planes, 2), dtype=torch.float32, device=z.device)
+        coef = torch.empty((round8(planes), 2), dtype=torch.float32, device=z.device)
+        ws = torch.empty((planes * ch * 2,), dtype=torch.float32, device=z.device)
+        with _timed(f"instnorm_stats_n{hw}", nbytes=1.0 * z.numel() * z.element_size()):
+            check(lib().mk_instnorm_stats_fused(ptr(z), dtype_code(z), ptr(stats), ptr(coef), ptr(ws), ptr(g), ptr(b), ptr(pb), planes, M,
+                                                hw, eps, stream()), "instnorm_stats_fused")
+        A, At = weight_operands(weight, need_t=ctx.needs_input_grad[0])
+        y = torch.empty((B, M, H, W), dtype=torch.bfloat16, device=z.device)
+        with _timed(f"conv1x1_nn_m{M}_k{K}_n{hw}", flops=2.0 * B * M * K * hw, nbytes=2.0 * B * hw * (2 * M + K)):
+            check(lib().mk_conv1x1_nn_rnorm(ptr(A), ptr(res), ptr(y), ptr(None), ptr(None), ptr(z), ptr(None), M, K, A.shape[1], B, hw, 0,
+                                            ptr(coef), ptr(pb), M, stream()), "mk_conv1x1_nn_rnorm")
+        ctx.save_for_backward(res, weight, At, z, stats, g, b, pb)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        res, weight, At, z, stats, g, b, pb = ctx.saved_tensors
+        B, M = z.shape[:2]
+        gy = gy.contiguous()
+        gres = gw = gz = gg = gb = gpb = None
+        if ctx.needs_input_grad[0]:
+            gres, _ = conv1x1_nn(At, M, gy)
+        if ctx.needs_input_grad[1]:
+            gw = conv1x1_wgrad(gy, res).view_as(weight)
+        if any(ctx.needs_input_grad[2:5]):
+            gz, sums = _instnorm_bwd(z, gy, stats, g, b, pb, None, 0.0, False)
+            s = _batch_sum(sums, B, M)
+            gg, gb = (s[1] if g is not None else None), (s[0] if b is not None else None)
+        if pb is not None and ctx.needs_input_grad[6]:
+            gpb = torch.zeros_like(pb)                   # (the plane sum of the norm's input gradient: exactly zero)
+        return gres, gw, gz, gg, gb, None, gpb
 
 
 class ConvGeluConvFn(torch.autograd.Function):

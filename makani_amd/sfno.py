@@ -24,7 +24,8 @@ from ._lib import device_guard
 from torch.utils.checkpoint import checkpoint
 
 from . import distributed as thd
-from .layers import MLP, ChannelLayerNorm, DropPath, EncoderDecoder, GeometricInstanceNormS2, InstanceNorm2d, PointwiseConv
+from .layers import (MLP, ChannelLayerNorm, DropPath, EncoderDecoder, GeometricInstanceNormS2, InstanceNorm2d, PointwiseConv,
+                     skip_norm, skip_norm_foldable)
 from .sht import InverseRealSHT, RealSHT
 from .spectral_conv import SpectralConv
 
@@ -101,13 +102,17 @@ class NeuralOperatorBlock(nn.Module):
         else:
             x = self.act_layer0(self.norm0(x))
 
+        pb = None
         if hasattr(self, "mlp") and type(self.norm1) is InstanceNorm2d and self.mlp.can_defer_output_bias(x):
             x, pb = self.mlp.forward_deferred_bias(x)         # fc2's bias rides in norm1 (same rounding as y + b)
-            x = self.norm1(x, pre_bias=pb)
-        else:
-            if hasattr(self, "mlp"):
-                x = self.mlp(x)
-            x = self.norm1(x)
+        elif hasattr(self, "mlp"):
+            x = self.mlp(x)
+        if (hasattr(self, "outer_skip") and isinstance(self.drop_path, nn.Identity)
+                and skip_norm_foldable(self.outer_skip, self.norm1, residual, x)):
+            # norm1's only consumer is the skip GEMM's residual operand: statistics pass + GEMM that normalises where it adds
+            x = skip_norm(self.outer_skip, self.norm1, residual, x, pre_bias=pb)
+            return self.act_layer1(x) if hasattr(self, "act_layer1") else x
+        x = self.norm1(x, pre_bias=pb) if pb is not None else self.norm1(x)
         x = self.drop_path(x)
 
         if hasattr(self, "outer_skip"):

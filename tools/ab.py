@@ -5,10 +5,13 @@ variant is only ever compared with the baseline inside ONE gpurun call).
        python tools/ab.py build base  rb8:-DMK_FFT_RB1440=8  nt256:-DMK_FFT_NT1440=256
    builds makani_amd/libmakani_amd_<tag>.so for every `tag[:-Dmacro=value,...]` (the kernel source must read the macro);
 2. on the GPU box, inside one gpurun call:
-       python tools/ab.py run [--timeout SECONDS] base rb8 nt256 -- python tools/microbench.py fft
+       python tools/ab.py run [--timeout SECONDS] [--repeat N] base rb8 nt256 -- python tools/microbench.py fft
    runs the command once per variant with MAKANI_AMD_LIB pointing at it and prints the outputs side by side.  A variant that
    exits non-zero or runs past its time limit (default 600 s per variant, sized for tools/microbench.py) is the LAST one
    started: after a fault nothing more may touch the GPU, so the outputs so far are printed and ab.py exits with that status.
+   An arm may carry environment settings, `tag@VAR=VALUE[,VAR=VALUE]` (a path that Python, not a macro, selects:
+   `parent@MAKANI_AMD_NORM1_FOLD=0 new`), and `--repeat N` runs the arms N times in alternation (parent new parent new: drift of
+   the box over the call hits both arms alike); the outputs are labelled `tag#k`.
 `base` without defines is the default library rebuilt under its own tag, so that all variants come from the same sources."""
 import os
 import subprocess
@@ -30,28 +33,32 @@ def build(specs):
         print(f"{tag}: {path}")
 
 
-def run(tags, cmd, timeout=600.0):
-    for tag in tags:
+def run(arms, cmd, timeout=600.0, repeat=1):
+    specs = []
+    for arm in arms:
+        tag, _, envs = arm.partition("@")
         if not os.path.exists(lib_of(tag)):
             raise SystemExit(f"{lib_of(tag)} is missing: run `python tools/ab.py build {tag}[:-D...]` first")
+        specs.append((tag, dict(e.split("=", 1) for e in envs.split(",") if e)))
+    runs = [(tag if repeat == 1 else f"{tag}#{k + 1}", tag, env) for k in range(repeat) for tag, env in specs]
     outs, status = {}, 0
-    for tag in tags:
+    for label, tag, env in runs:
         try:
-            r = subprocess.run(cmd, env=dict(os.environ, MAKANI_AMD_LIB=lib_of(tag)), capture_output=True, text=True, timeout=timeout)
+            r = subprocess.run(cmd, env=dict(os.environ, MAKANI_AMD_LIB=lib_of(tag), **env), capture_output=True, text=True, timeout=timeout)
             text, status = r.stdout + r.stderr, r.returncode
         except subprocess.TimeoutExpired as e:                 # (subprocess.run has killed and reaped the child)
             text = "".join(t.decode(errors="replace") if isinstance(t, bytes) else t for t in (e.stdout, e.stderr) if t)
             status = 124
-        outs[tag] = [l for l in text.splitlines() if l.strip() and "amdgpu.ids" not in l]
+        outs[label] = [l for l in text.splitlines() if l.strip() and "amdgpu.ids" not in l]
         if status:
-            print(f"[{tag}] {'ran past its time limit of %g s' % timeout if status == 124 else 'exit code %d' % status}: "
-                  f"not starting {[t for t in tags if t not in outs] or 'anything else'}")
+            print(f"[{label}] {'ran past its time limit of %g s' % timeout if status == 124 else 'exit code %d' % status}: "
+                  f"not starting {[l for l, _, _ in runs if l not in outs] or 'anything else'}")
             break
     n = max(len(v) for v in outs.values())
     for i in range(n):
-        for tag in outs:
-            line = outs[tag][i] if i < len(outs[tag]) else ""
-            print(f"{tag:>10s} | {line}")
+        for label in outs:
+            line = outs[label][i] if i < len(outs[label]) else ""
+            print(f"{label:>10s} | {line}")
         print()
     return status
 
@@ -63,7 +70,11 @@ if __name__ == "__main__":
         build(sys.argv[2:])
     else:
         args = sys.argv[2:sys.argv.index("--")]
-        limit = 600.0
-        if args and args[0] == "--timeout":
-            limit, args = float(args[1]), args[2:]
-        sys.exit(run(args, sys.argv[sys.argv.index("--") + 1:], limit))
+        limit, repeat = 600.0, 1
+        while args and args[0] in ("--timeout", "--repeat"):
+            if args[0] == "--timeout":
+                limit = float(args[1])
+            else:
+                repeat = int(args[1])
+            args = args[2:]
+        sys.exit(run(args, sys.argv[sys.argv.index("--") + 1:], limit, repeat))

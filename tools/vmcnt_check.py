@@ -245,25 +245,29 @@ def check_isa(path=None, verbose=True):
 # the two-group form (conv_nn_astat2_kernel): both groups' instruction streams against the same retirement model
 # --------------------------------------------------------------------------- #
 class Variant2:
-    """compile-time constants of conv_nn_astat2_kernel<PRE, EPI_LOADS>"""
+    """compile-time constants of conv_nn_astat2_kernel<PRE, EPI_LOADS, RNORM>.  RNORM (the residual operand normalised where the
+    epilogue adds it) loads its coefficients in the prologue and moves them between lanes with ds_bpermute_b32 (lgkmcnt): the
+    vector-memory stream, and with it every count, is that of <PRE = 0, EPI_LOADS = 1> — which check_isa2 verifies on the
+    compiled kernel (no vector load behind the first DMA piece, the same stores, the same immediates)."""
     NP, NCH, PER, OFF = 2, 3, 7, 3
     # [group][kc]: chunk requests / read-back rounds / operand requests behind a chunk
     WA = ((3, 2, 1), (3, 2, 1))
     WB = ((3, 2, 1), (3, 1, 2))
     WE = ((1, 1, 1), (1, 0, 0))
 
-    def __init__(self, PRE, EPI):
-        self.PRE, self.EPI = PRE, EPI
+    def __init__(self, PRE, EPI, RNORM=False):
+        assert not RNORM or (EPI and not PRE)
+        self.PRE, self.EPI, self.RNORM = PRE, EPI, RNORM
         self.NSLOT = 4
         self.NS3 = 2 * (2 if PRE else 1)
         self.EPIECES = 6 if EPI else 0
 
     @property
     def name(self):
-        return f"astat2<PRE={int(self.PRE)}, EPI_LOADS={int(self.EPI)}>"
+        return f"astat2<PRE={int(self.PRE)}, EPI_LOADS={int(self.EPI)}, RNORM={int(self.RNORM)}>"
 
     def mangled(self):
-        return f"21conv_nn_astat2_kernelILb{int(self.PRE)}ELb{int(self.EPI)}EE"
+        return f"21conv_nn_astat2_kernelILb{int(self.PRE)}ELb{int(self.EPI)}ELb{int(self.RNORM)}EE"
 
     def wait_const(self, g, kc):
         return self.WA[g][kc] * self.NP + self.WB[g][kc] * self.NS3 + self.WE[g][kc] * self.EPIECES
@@ -278,7 +282,7 @@ class Variant2:
         return {0} | {self.wait_const(g, k) for g in (0, 1) for k in range(3)} | ({3 * self.NP} if self.EPI else set())
 
 
-VARIANTS2 = [Variant2(pre, epi) for pre in (False, True) for epi in (False, True)]
+VARIANTS2 = [Variant2(pre, epi) for pre in (False, True) for epi in (False, True)] + [Variant2(False, True, True)]
 
 
 def simulate2(v: Variant2, T: int):
@@ -355,7 +359,7 @@ def check_model2(verbose=True):
         steady = max(simulate2(v, T) for T in list(range(0, 12)) + [31, 64])
         assert steady == 0, f"{v.name}: a steady-state wait fires {steady} instructions early"
         if verbose:
-            print(f"model ok  {v.name:40s} slots={v.NSLOT} waits " +
+            print(f"model ok  {v.name:49s} slots={v.NSLOT} waits " +
                   " ".join(f"g{g}k{k}={v.wait_const(g, k)}" for g in (0, 1) for k in range(3)) + f"  LDS {lds // 1024} KB")
 
 
@@ -380,7 +384,7 @@ def check_isa2(path=None, verbose=True):
         nstores = sum(1 for o in ops if o.startswith("buffer_store_dwordx4"))
         assert nstores and nstores % v.NS3 == 0
         if verbose:
-            print(f"isa ok    {v.name:40s} {nstores} stores, vmcnt {sorted(imm)}")
+            print(f"isa ok    {v.name:49s} {nstores} stores, vmcnt {sorted(imm)}")
 
 
 if __name__ == "__main__":
