@@ -473,6 +473,24 @@ int mk_amse_sums(const float* X, const float* Y, const float* wgt, float* sums, 
 int mk_amse_grad(const float* X, const float* Y, const float* wgt, const float* t, float* dX, float* dY, long long R, int L, int M,
                  int tri_off, int m_off, void* stream);
 
+/* ---- per-degree ensemble Gram matrix in spectral space (SpectralCoherenceLoss, makani/utils/losses/energy_score.py:655-856;
+ * CoherenceRegularization and SpectralRegularization, makani/utils/losses/regularization.py:84-417; makani_amd/csrc/egram.hip).
+ * f: (B, E, C, L, M) complex64 members (re, im interleaved), o: (B, C, L, M) complex64 observation, q: (L, M) f32 weights with every
+ * constant folded in (1 / 4 pi, 2 for m > 0, 0 for m > l).  Fields x_0 .. x_{E-1} = members, x_E = observation, n = E + 1.
+ * mk_egram_sums: G (B, C, L, K) f32, G[i][j] = sum_m q Re(conj(x_i) x_j); slots of a row: [0, n) G[i][i]; [n, n + E) G[e][E];
+ *   [n + E, n + E + E (E - 1) / 2) G[i][j], i < j < E, lexicographic.  `what` truncates the row: DIAG K = n, OBS K = n + E, FULL all.
+ * mk_egram_grad: dG (B, C, L, K) -> gf (B, E, C, L, M) complex64 = q (2 dG[e][e] x_e + dG[e][E] x_E + sum_{j != e} dG[e, j] x_j) in
+ *   torch's complex-gradient convention; the observation gets none.
+ * Orders m > l + tri_off are not read (q is 0 there) and get exact zeros in gf; tri_off >= M skips nothing.  1 <= E <= 32, more:
+ * MK_EUNSUP. */
+#define MK_EGRAM_DIAG 0
+#define MK_EGRAM_OBS 1
+#define MK_EGRAM_FULL 2
+int mk_egram_sums(const void* f, const void* o, const float* q, float* G, int B, int E, int C, int L, int M, int what, int tri_off,
+                  void* stream);
+int mk_egram_grad(const void* f, const void* o, const float* q, const float* dG, void* gf, int B, int E, int C, int L, int M, int what,
+                  int tri_off, void* stream);
+
 /* ---- Gaussian negative log likelihood of an ensemble (EnsembleNLLLoss, makani/utils/losses/likelihood_loss.py:30-134) ----
  * f: (B, E, C, hw) members f32 | bf16, obs: (B, C, hw) f32, q: (hw), w: optional (B, C, hw) f32.
  * nll = 0.5 (log s2 + (obs - mu)^2 / s2), mu the ensemble mean, s2 = max(centred variance (correction 0), eps^2).

@@ -9,6 +9,7 @@ from .sfno import SphericalFourierNeuralOperatorNet, NeuralOperatorBlock, Spectr
 from .losses import CRPSLoss, GradientCRPSLoss, VortDivCRPSLoss, GeometricLpLoss, GridQuadrature, SpectralCRPSLoss, SpectralLpLoss, SpectralH1Loss
 from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss, SpectralL2EnergyScoreLoss
 from .losses import SpectralAMSELoss, EnsembleNLLLoss, GaussianMMDLoss
+from .losses import SpectralCoherenceLoss, CoherenceRegularization, SpectralRegularization, EnsembleGramFn
 from .metrics import (GeometricL1, GeometricRMSE, GeometricACC, GeometricSpread, GeometricSSR, GeometricCRPS, GeometricRankHistogram,
                       deterministic_sums)
 from .stepper import MultiStepWrapper, SingleStepWrapper
@@ -28,6 +29,7 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DiscreteContinuousConvS2", "ResampleS2", "AtmoSphericNeuralOperatorNet",
            "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
            "SpectralAMSELoss", "EnsembleNLLLoss", "GaussianMMDLoss",
+           "SpectralCoherenceLoss", "CoherenceRegularization", "SpectralRegularization", "EnsembleGramFn",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
            "deterministic_sums",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",

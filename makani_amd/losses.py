@@ -938,6 +938,18 @@ class LpEnergyScoreLoss(_EnergyScoreMixin, _EnsembleLoss):
 L2EnergyScoreLoss = LpEnergyScoreLoss          # backward-compatibility alias, as the reference's
 
 
+def _ensemble_split_lm(f, o, q):
+    """f (B, E_loc, C, L, M) complex, o (B, C, L, M), q (L, M): the members of the group on this rank's share of the
+    orders m (the reference's ``distributed_transpose(..., (-1, 0))`` of the last axis).  The exchange moves real tensors:
+    (re, im) travel as two rows of the channel axis."""
+    B, E, Cc, L, M = f.shape
+    fr = torch.view_as_real(f.contiguous()).permute(0, 1, 2, 3, 5, 4).reshape(B, E, Cc * L * 2, M)
+    fr, os_, qs, _, group = ensemble_split(fr, o, q, None)
+    Ml = fr.shape[-1]
+    fs = torch.view_as_complex(fr.reshape(B, -1, Cc, L, 2, Ml).permute(0, 1, 2, 3, 5, 4).contiguous())
+    return fs, os_, qs, group
+
+
 class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
     """the spectral energy scores: HIP ``RealSHT`` of members and observation (fp32, autocast off, / sqrt(4 pi)), then the
     kernels of ``csrc/escore.hip`` on the complex coefficients (squared modulus; a coefficient where the observation or any
@@ -953,16 +965,7 @@ class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
 
     type = _EnsembleLoss.type                                                   # (the rest of that base belongs to the grid)
 
-    def _ensemble_split_lm(self, f, o, q):
-        """f (B, E_loc, C, L, M) complex, o (B, C, L, M), q (L, M): the members of the group on this rank's share of the
-        orders m (the reference's ``distributed_transpose(..., (-1, 0))`` of the last axis).  The exchange moves real tensors:
-        (re, im) travel as two rows of the channel axis."""
-        B, E, Cc, L, M = f.shape
-        fr = torch.view_as_real(f.contiguous()).permute(0, 1, 2, 3, 5, 4).reshape(B, E, Cc * L * 2, M)
-        fr, os_, qs, _, group = ensemble_split(fr, o, q, None)
-        Ml = fr.shape[-1]
-        fs = torch.view_as_complex(fr.reshape(B, -1, Cc, L, 2, Ml).permute(0, 1, 2, 3, 5, 4).contiguous())
-        return fs, os_, qs, group
+    _ensemble_split_lm = staticmethod(_ensemble_split_lm)          # (shared with the coherence losses below)
 
     def _score(self, forecasts, observations, per_degree):
         from . import comm as _comm
@@ -1227,3 +1230,290 @@ class GaussianMMDLoss(_EnergyScoreMixin, _EnsembleLoss):
         f, o, q, w, groups = self._points(forecasts, observations, spatial_weights)
         ensemble_size_check(f.shape[1], "MMD")
         return EnergyScoreFn.apply(f, o, q, w, 1, 1, self.channel_reduction, self.beta, _mmd_finish(self.sigma, self.alpha), groups)
+
+
+# --------------------------------------------------------------------------- #
+# spectral coherence losses on the per-degree ensemble Gram matrix (energy_score.py:655-856, regularization.py:84-417)
+# --------------------------------------------------------------------------- #
+EGRAM_DIAG, EGRAM_OBS, EGRAM_FULL = (_lib.CONSTS["MK_EGRAM_" + k] for k in ("DIAG", "OBS", "FULL"))
+EGRAM_TRI_NONE = 1 << 30          # `tri_off` of a caller that cannot name the triangle's offset: no order is skipped
+
+
+def egram_slots(E, what):
+    """K, the length of a row of ``mk_egram_sums`` for ``E`` members"""
+    n = E + 1
+    return {EGRAM_DIAG: n, EGRAM_OBS: n + E, EGRAM_FULL: n + E + E * (E - 1) // 2}[what]
+
+
+def egram_slot(i, j, E):
+    """slot of G[i][j] = G[j][i] in a row; fields 0 .. E - 1 are the members, field E is the observation: the diagonal, then the
+    member-observation column, then the member pairs i < j in lexicographic order"""
+    i, j = min(i, j), max(i, j)
+    if not 0 <= i <= j <= E:
+        raise IndexError(f"G[{i}][{j}] of an ensemble of {E}")
+    if i == j:
+        return i
+    if j == E:
+        return E + 1 + i
+    return 2 * E + 1 + i * (2 * E - i - 1) // 2 + (j - i - 1)
+
+
+def parseval_triangle_weights(lmax, mmax):
+    """(lmax, mmax): 1 for m = 0, 2 for m > 0, 0 for m > l — the ``lm_weights`` / ``m_weights`` of the three reference classes"""
+    w = torch.ones((lmax, mmax), dtype=torch.float32)
+    w[:, 1:] *= 2.0
+    ls, ms = torch.arange(lmax).reshape(-1, 1), torch.arange(mmax).reshape(1, -1)
+    return torch.where(ms > ls, 0.0, w)
+
+
+def egram_weights(lmax, mmax, l_off=0, m_off=0, l_loc=None, m_loc=None):
+    """(q, tri_off) of ``mk_egram_sums`` for the shard [l_off, l_off + l_loc) x [m_off, m_off + m_loc) of the (lmax, mmax)
+    coefficient plane: q carries every constant (1 / 4 pi — the reference's ``/ sqrt(4 pi)`` on the coefficients —, the factor
+    2 of m > 0, the zeros of m > l); local order m of local degree l is structurally zero for m > l + tri_off"""
+    l_loc = lmax - l_off if l_loc is None else l_loc
+    m_loc = mmax - m_off if m_loc is None else m_loc
+    q = parseval_triangle_weights(lmax, mmax)[l_off:l_off + l_loc, m_off:m_off + m_loc] / (4.0 * math.pi)
+    return q.contiguous(), l_off - m_off
+
+
+class EnsembleGramFn(torch.autograd.Function):
+    """``csrc/egram.hip``: f (B, E, C, L, M) complex64 members, o (B, C, L, M) complex64 observation, q (L, M) -> G (B, C, L, K)
+    f32, the Parseval-weighted Hermitian Gram matrix of the E + 1 fields per degree in the slot order of ``egram_slot``,
+    truncated by ``what`` (``EGRAM_DIAG`` | ``EGRAM_OBS`` | ``EGRAM_FULL``).  The sums are added over ``sum_groups`` inside
+    (the backward of a SUM all-reduce is the identity).  Gradient with respect to the members only."""
+
+    @staticmethod
+    def forward(ctx, f, o, q, what, tri_off, sum_groups):
+        B, E, Cc, L, M = f.shape
+        ensemble_size_check(E, "coherence")
+        fr = torch.view_as_real(f.to(torch.complex64).contiguous())
+        orr = torch.view_as_real(o.to(torch.complex64).contiguous())
+        q = q.float().contiguous()
+        if tuple(orr.shape) != (B, Cc, L, M, 2) or tuple(q.shape) != (L, M):
+            raise ValueError(f"members {tuple(f.shape)}, observation {tuple(o.shape)} and weights {tuple(q.shape)} do not fit")
+        G = torch.empty((B, Cc, L, egram_slots(E, what)), dtype=torch.float32, device=fr.device)
+        check(lib().mk_egram_sums(ptr(fr), ptr(orr), ptr(q), ptr(G), B, E, Cc, L, M, what, int(tri_off), stream()), "mk_egram_sums")
+        from . import ops
+        for group in sum_groups:
+            ops._all_reduce_sum(G, group)
+        ctx.save_for_backward(fr, orr, q)
+        ctx.meta = (what, int(tri_off))
+        return G
+
+    @staticmethod
+    def backward(ctx, g):
+        fr, orr, q = ctx.saved_tensors
+        what, tri_off = ctx.meta
+        B, E, Cc, L, M = fr.shape[:5]
+        dG = g.float().contiguous()
+        gf = torch.empty_like(fr)
+        check(lib().mk_egram_grad(ptr(fr), ptr(orr), ptr(q), ptr(dG), ptr(gf), B, E, Cc, L, M, what, tri_off, stream()), "mk_egram_grad")
+        return torch.view_as_complex(gf), None, None, None, None, None
+
+
+class _EnsembleGramLoss(SpectralLpLoss):
+    """what the three coherence losses share: the HIP ``RealSHT`` of members and observation (fp32, autocast off, raw
+    coefficients: the 1 / 4 pi lives in the weights), ``EnsembleGramFn`` on them, and the sums over the process groups — the
+    ensemble group (members <-> a share of the orders) and "w" inside the function, "h" on the loss"""
+
+    def __init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed, ensemble_distributed, eps):
+        SpectralLpLoss.__init__(self, img_shape, crop_shape, crop_offset, channel_names, grid_type,
+                                spatial_distributed=spatial_distributed, lmax=lmax, eps=eps)
+        self.ensemble_distributed = ensemble_active(ensemble_distributed)
+        Ll, Ml = self.lm_weights.shape
+        q, self._tri_off = egram_weights(self.sht.lmax, self.sht.mmax, self._l_off, self._m_off, Ll, Ml)
+        self.register_buffer("gram_weights", q, persistent=False)
+
+    type = _EnsembleLoss.type
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    def _local_triangle_weights(self):
+        Ll, Ml = self.gram_weights.shape
+        w = parseval_triangle_weights(self.sht.lmax, self.sht.mmax)
+        return w[self._l_off:self._l_off + Ll, self._m_off:self._m_off + Ml].contiguous()
+
+    def _gram(self, forecasts, observations, what, gather_members=True):
+        """forecasts (B, E, C, H, W), observations (B, C, H, W) -> G (B, C, L, K) summed over the orders of all ranks, and
+        the number of members in it"""
+        from . import comm as _comm
+        if not (self.ensemble_distributed and gather_members):          # (else the members of the group are counted below)
+            ensemble_size_check(forecasts.shape[1], "coherence")
+        need_gpu(forecasts)
+        with torch.autocast(device_type=forecasts.device.type, enabled=False):
+            f = self.sht(forecasts.float())
+            o = self.sht(observations.float())
+        q, tri_off, groups = self.gram_weights, self._tri_off, []
+        if self.ensemble_distributed and gather_members:
+            f, o, q, group = _ensemble_split_lm(f, o, q)
+            groups.append(group)
+            tri_off = EGRAM_TRI_NONE                # (this rank's share of the orders: q holds the zeros, nothing is skipped)
+        if self.spatial_distributed and _comm.get_size("w") > 1:
+            groups.append(_comm.get_group("w"))
+        E = f.shape[1]
+        ensemble_size_check(E, "coherence")
+        return EnsembleGramFn.apply(f, o, q, what, tri_off, groups), E
+
+    def _sum_degrees(self, loss):
+        """(B, C, L) -> (B, C): the local degrees, then the "h" group"""
+        from . import comm as _comm
+        loss = loss.sum(dim=-1)
+        if self.spatial_distributed and _comm.get_size("h") > 1:
+            loss = ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+        return loss
+
+
+def _pair_decoherence(psd_f, pairs, E, eps):
+    """sum_{i != j} (1 - coh_ij) / (E (E - 1)) from the pair slots (each unordered pair counts twice); exactly 0 for E = 1"""
+    if E < 2:
+        return torch.zeros_like(psd_f[..., 0])
+    iu = torch.triu_indices(E, E, 1, device=psd_f.device)          # (lexicographic: the slot order)
+    coh = pairs / torch.sqrt(psd_f[..., iu[0]] * psd_f[..., iu[1]] + eps)
+    return 2.0 * (1.0 - coh).sum(dim=-1) / float(E * (E - 1))
+
+
+class SpectralCoherenceLoss(_EnsembleGramLoss):
+    """``SpectralCoherenceLoss`` of ``makani/utils/losses/energy_score.py:655-856``: per degree l the error of the members'
+    power spectral density against the observation's plus ``2 PSD_o (mean_e (1 - coh(f_e, o)) - 1/2 mean_{i != j} (1 -
+    coh(f_i, f_j)))`` (``relative``: the PSD error divided by ``PSD_o + eps`` and no ``PSD_o`` factor), summed over l.
+    ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W)) -> (B, C) | (B, 1)``.  HIP SHT (fp32, autocast off), then
+    ONE kernel for the whole per-degree Gram matrix of members and observation (``csrc/egram.hip``, ``EGRAM_FULL``) and one for
+    the gradient: no (E, E, B, C, L, M) product exists, the finish works on the (B, C, L, K) sums in fp32 torch.  ``alpha`` and
+    ``ensemble_weights`` are accepted and unused, as in the reference; E = 1 gives a spread of exactly 0.
+    ``spatial_distributed``: the sums are added over "w" before the finish, the loss over "h" after it; ``ensemble_distributed``:
+    the members are gathered on this rank's share of the orders and the sums added over the ensemble group.
+
+    Deviations, stated: CPU tensors raise (the HIP path has no CPU fallback); more than 32 members raise NotImplementedError."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, relative: Optional[bool] = False,
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
+                 ensemble_weights: Optional[torch.Tensor] = None, channel_reduction: Optional[bool] = True,
+                 alpha: Optional[float] = 1.0, eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, eps)
+        self.relative, self.channel_reduction = relative, channel_reduction
+        self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
+        self.register_buffer("lm_weights", self._local_triangle_weights(), persistent=False)
+
+    @property
+    def n_channels(self):
+        return 1 if self.channel_reduction else len(self.channel_names)
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: str = None) -> torch.Tensor:
+        if self.channel_reduction:
+            return torch.ones(1)
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        check_forecast_dims(forecasts)
+        G, E = self._gram(forecasts, observations, EGRAM_FULL)
+        n = E + 1
+        psd_f, psd_o, cross, pairs = G[..., :E], G[..., E:n], G[..., n:n + E], G[..., n + E:]
+        coh_obs = cross / torch.sqrt(psd_f * psd_o + self.eps)
+        psd_skill = (psd_f - psd_o).square()
+        if self.relative:
+            psd_skill = psd_skill / (psd_o + self.eps)
+        psd_skill = psd_skill.sum(dim=-1) / float(E)
+        coh_skill = (1.0 - coh_obs).sum(dim=-1) / float(E)
+        coh_spread = _pair_decoherence(psd_f, pairs, E, self.eps)
+        loss = 2.0 * (coh_skill - 0.5 * coh_spread)
+        loss = psd_skill + (loss if self.relative else psd_o.squeeze(-1) * loss)
+        loss = self._sum_degrees(loss)
+        return loss.sum(dim=-1, keepdim=True) if self.channel_reduction else loss
+
+
+class CoherenceRegularization(_EnsembleGramLoss):
+    """``CoherenceRegularization`` of ``makani/utils/losses/regularization.py:215-417``: the mean over the band ``[lmin, lmax)``
+    of ``1 - mean_e coh_l(f_e, o)`` with the signed per-degree coherence ``CrossPSD / sqrt(PSD_f PSD_o + eps)``, plus
+    ``ensemble_coherence_weight * mean_{i != j} (1 - coh_l(f_i, f_j))`` when that weight is non-zero and E > 1.
+    ``forward(forecasts (B, E, C, H, W), observations (B, C, H, W)) -> (B, C)``.  HIP SHT, then ``csrc/egram.hip``: ``EGRAM_FULL``
+    only when the inter-member term is active, else ``EGRAM_OBS`` (PSDs and member-observation cross spectra: every member
+    coefficient is read once); the finish works on the (B, C, L, K) sums in fp32 torch.  Parallel forms as
+    ``SpectralCoherenceLoss``; ``band_size`` is the global width of the band.
+
+    Deviations, stated: CPU tensors raise (the HIP path has no CPU fallback); more than 32 members raise NotImplementedError."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmin: Optional[int] = None, lmax: Optional[int] = None,
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
+                 ensemble_weights: Optional[torch.Tensor] = None, ensemble_coherence_weight: Optional[float] = 0.0,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, eps)
+        self.ensemble_coherence_weight = ensemble_coherence_weight
+        self.register_buffer("ensemble_weights", ensemble_weights, persistent=False)
+        self.lmin = lmin if lmin is not None else 0
+        if self.lmin >= self.sht.lmax:
+            raise ValueError(f"Error, lmin ({self.lmin}) must be smaller than the SHT truncation lmax ({self.sht.lmax}), otherwise "
+                             "the band is empty.")
+        l_band = torch.zeros(self.sht.lmax)
+        l_band[self.lmin:self.sht.lmax] = 1.0
+        band_size = l_band.sum().clamp(min=1.0)                                     # the global width (:307-310)
+        Ll = self.gram_weights.shape[0]
+        self.register_buffer("m_weights", self._local_triangle_weights(), persistent=False)
+        self.register_buffer("l_band", l_band[self._l_off:self._l_off + Ll].contiguous(), persistent=False)
+        self.register_buffer("band_size", band_size, persistent=False)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        if forecasts.dim() != 5:
+            raise ValueError(f"Error, forecasts expected 5 dims, got {forecasts.dim()}.")
+        from .comm import get_size
+        E_all = forecasts.shape[1] * (get_size("ensemble") if self.ensemble_distributed else 1)
+        inter = (self.ensemble_coherence_weight != 0.0) and (E_all > 1)
+        G, E = self._gram(forecasts, observations, EGRAM_FULL if inter else EGRAM_OBS)
+        n = E + 1
+        psd_f, psd_o, cross = G[..., :E], G[..., E:n], G[..., n:n + E]
+        coh_obs = cross / torch.sqrt(psd_f * psd_o + self.eps)
+        loss = (1.0 - coh_obs).sum(dim=-1) / float(E)
+        if inter:
+            loss = loss + self.ensemble_coherence_weight * _pair_decoherence(psd_f, G[..., n + E:], E, self.eps)
+        return self._sum_degrees(self.l_band * loss) / self.band_size
+
+
+class SpectralRegularization(_EnsembleGramLoss):
+    """``SpectralRegularization`` of ``makani/utils/losses/regularization.py:84-212``: ``sum_l |PSD_l(f_e) - PSD_l(o)|``
+    (``logarithmic``: of the logarithms), averaged over the members and divided by the global ``sht.lmax``.
+    ``forward(forecasts (B, E, C, H, W) | (B, C, H, W), observations (B, C, H, W)) -> (B, C)``; 4-dimensional forecasts count
+    as one member.  HIP SHT, then ``csrc/egram.hip`` with ``EGRAM_DIAG`` (the diagonal only: every coefficient is read once for
+    every E); the finish works on the (B, C, L, E + 1) sums in fp32 torch.  ``spatial_distributed`` as ``SpectralCoherenceLoss``;
+    ``ensemble_distributed``: the members stay local, the member mean is summed over the ensemble group and divided by its size.
+
+    Deviations, stated: CPU tensors raise (the HIP path has no CPU fallback); more than 32 local members raise
+    NotImplementedError."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, eps: Optional[float] = 1.0e-10, logarithmic: Optional[bool] = False,
+                 **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, eps)
+        self.logarithmic = logarithmic
+        self.register_buffer("lm_weights", self._local_triangle_weights(), persistent=False)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        if forecasts.dim() == 4:
+            forecasts, members = forecasts.unsqueeze(1), False
+        elif forecasts.dim() == 5:
+            members = True
+        else:
+            raise ValueError(f"Error, forecasts tensor expected to have 4 or 5 dimensions but found {forecasts.dim()}.")
+        G, E = self._gram(forecasts, observations, EGRAM_DIAG, gather_members=False)
+        psd_f, psd_o = G[..., :E], G[..., E:]
+        if self.logarithmic:
+            psd_f, psd_o = torch.log(psd_f), torch.log(psd_o)
+        diff = (psd_f - psd_o).abs().sum(dim=-1) / float(E)
+        if members and self.ensemble_distributed:
+            from . import comm as _comm
+            diff = ReduceFromGroupFn.apply(diff, _comm.get_group("ensemble")) / float(_comm.get_size("ensemble"))
+        return self._sum_degrees(diff) / float(self.sht.lmax)

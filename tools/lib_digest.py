@@ -1,7 +1,7 @@
 """SHA-256 of every output of the kernels that share csrc/block_io.h, on fixed inputs at small shapes, from whichever library
 MAKANI_AMD_LIB names.  Two builds whose arithmetic and summation orders agree print the same lines:
        python tools/ab.py run parent new -- python tools/lib_digest.py
-   python tools/lib_digest.py [crps] [nll] [metrics] [escore] [preproc] [layernorm] [resample] [disco] [optim]
+   python tools/lib_digest.py [crps] [nll] [metrics] [escore] [egram] [preproc] [layernorm] [resample] [disco] [optim]
 Shapes: 33 x 40 points (a multiple of 4, two chunks of a plane) and 33 x 41 (odd: one element per thread), bases aligned and
 shifted by one element, both element types, ensembles of 2, 3, 5, 9 and 17 (every compiled capacity, each partly filled)."""
 import ctypes as C
@@ -55,6 +55,19 @@ def crps():
         for grad in (0, 1):
             check(lib().mk_crps_complex(ptr(f), ptr(o), ptr(q), ptr(w), ptr(gout), ptr(part), ptr(gf), B, E, C, hw, 0.9, grad, stream()))
         emit(f"crps_complex E={E}", part, gf)
+
+
+def egram():
+    B, C, L, M = 2, 3, 5, 70
+    q = rnd(L, M, pos=True)
+    for E in (1,) + ES + (32,):
+        f, o = torch.view_as_complex(rnd(B, E, C, L, M, 2)), torch.view_as_complex(rnd(B, C, L, M, 2))
+        for what, K in ((0, E + 1), (1, 2 * E + 1), (2, 2 * E + 1 + E * (E - 1) // 2)):
+            for tri_off in (0, M):
+                G, dG, gf = torch.zeros(B, C, L, K, device=dev), rnd(B, C, L, K), torch.zeros_like(f)
+                check(lib().mk_egram_sums(ptr(f), ptr(o), ptr(q), ptr(G), B, E, C, L, M, what, tri_off, stream()))
+                check(lib().mk_egram_grad(ptr(f), ptr(o), ptr(q), ptr(dG), ptr(gf), B, E, C, L, M, what, tri_off, stream()))
+                emit(f"egram E={E} what={what} tri_off={tri_off}", G, gf)
 
 
 def nll():
@@ -212,5 +225,5 @@ def optim():
 
 if __name__ == "__main__":
     print(f"library {_lib.LIB_PATH}", file=sys.stderr)
-    for fam in sys.argv[1:] or ["crps", "nll", "metrics", "escore", "preproc", "layernorm", "resample", "disco", "optim"]:
+    for fam in sys.argv[1:] or ["crps", "nll", "metrics", "escore", "egram", "preproc", "layernorm", "resample", "disco", "optim"]:
         globals()[fam]()

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [metrics] [preproc] [constraints] [interpolant]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -423,6 +423,58 @@ def losses():
                 tt = timeit(fb(mmd_torch, f), reps=5, warm=2)
                 line += f" | torch formula {tt:7.3f} ms = {tt / tk:5.1f} x"
             print(line, flush=True)
+        del f, o
+    coherence()
+
+
+def coherence():
+    """The per-degree ensemble Gram kernels (csrc/egram.hip) with the finish of SpectralCoherenceLoss, forward + backward, on the
+    coefficient planes of a 721 x 1440 grid (L = M = 360), C = 73, B = 1, E = 2 and 16, beside the reference formulation in plain
+    torch (broadcast products, the (E, E, B, C, L, M) tensor) on the same GPU, in the same process, the two timed in turn over
+    three rounds.  Achieved bytes/s over the SINGLE-PASS traffic (members + observation read in each direction, the member
+    gradient written) as a fraction of the HBM roof; the kernel re-reads tiles for E > 7 and skips the orders m > l.  Also part
+    of `losses`."""
+    from makani_amd.losses import EGRAM_FULL, EnsembleGramFn, _pair_decoherence, egram_weights
+    PEAK = 8.0e12
+    B, C, L = 1, 73, 360
+    M = L
+    q, tri_off = egram_weights(L, M)
+    q = q.to(dev)
+    qt = q * (4.0 * math.pi)
+    eps = 1.0e-6
+    pct = lambda nbytes, ms: nbytes / (ms * 1e-3) / PEAK * 100
+    for E in (2, 16):
+        f = torch.randn(B, E, C, L, M, dtype=torch.complex64, device=dev).requires_grad_(True)
+        o = torch.randn(B, C, L, M, dtype=torch.complex64, device=dev)
+        n = E + 1
+
+        def finish(psd_f, psd_o, cross, spread):
+            coh = (1.0 - cross / torch.sqrt(psd_f * psd_o + eps)).sum(dim=-1) / E - 0.5 * spread
+            return ((psd_f - psd_o).square().sum(dim=-1) / E + 2.0 * psd_o.squeeze(-1) * coh).sum(dim=-1)
+
+        def kernel():
+            f.grad = None
+            G = EnsembleGramFn.apply(f, o, q, EGRAM_FULL, tri_off, [])
+            psd_f = G[..., :E]
+            finish(psd_f, G[..., E:n], G[..., n:n + E], _pair_decoherence(psd_f, G[..., n + E:], E, eps)).sum().backward()
+
+        def formula():
+            f.grad = None
+            fe = torch.moveaxis(f, 1, 0) / math.sqrt(4.0 * math.pi)
+            oe = o.unsqueeze(0) / math.sqrt(4.0 * math.pi)
+            psd_f = (qt * fe.abs().square()).sum(dim=-1)
+            psd_o = (qt * oe.abs().square()).sum(dim=-1)
+            pairs = (qt * (fe.unsqueeze(0).conj() * fe.unsqueeze(1)).real).sum(dim=-1)
+            cross = (qt * (fe.conj() * oe).real).sum(dim=-1)
+            coh_f = pairs / torch.sqrt(psd_f.unsqueeze(0) * psd_f.unsqueeze(1) + eps)
+            spread = torch.where(torch.eye(E, device=dev).bool().reshape(E, E, 1, 1, 1), 0.0, 1.0 - coh_f).sum(dim=(0, 1)) / (E * (E - 1))
+            finish(torch.movedim(psd_f, 0, -1), torch.movedim(psd_o, 0, -1), torch.movedim(cross, 0, -1), spread).sum().backward()
+
+        nbytes = B * C * L * M * 8 * (2 * n + E)
+        for rnd in range(3):
+            tk, tt = timeit(kernel, reps=20, warm=3), timeit(formula, reps=3, warm=1)
+            print(f"coherence E={E:2d} on ({B}, {E}, {C}, {L}, {M}) round {rnd}: fwd + bwd {tk:7.3f} ms {pct(nbytes, tk):5.1f} % of the HBM roof "
+                  f"on single-pass traffic ({nbytes / 1e9:.2f} GB) | torch formulation {tt:7.3f} ms = {tt / tk:5.1f} x", flush=True)
         del f, o
 
 
