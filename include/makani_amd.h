@@ -760,6 +760,54 @@ int mk_si_step(const void* x, long long x_stride, int x_dtype, const void* b, in
 int mk_si_step_bwd(const void* g, int g_dtype, void* gx0, int gx0_dtype, void* gx, int gx_dtype, void* gb, int gb_dtype, float cx, float cb,
                    float c0, int last, int B, int C, int Cin, long long HW, void* stream);
 
+/* ---- hydrostatic-balance loss and the loss handler's preparation pass (csrc/hydro.hip; makani/utils/losses/hydrostatic_loss.py,
+ *      makani/utils/loss.py:392-429) -----------------------------------------------------------------------------------------------
+ * x (N, C, HW) f32 | bf16 contiguous, read in place; the arithmetic is fp32.  Per sample n and level interval k < K - 1
+ *     Z_k = zs_k x[z_ch[k]] + zb_k,   T_k = ts_k x[t_ch[k]] + tb_k,   NQ = K: T_k *= f_k = 1 + eps (qs_k x[q_ch[k]] + qb_k)
+ *     r_k = (Z_{k+1} - Z_k) + hl_k (T_k + T_{k+1})
+ *         = hl_k (d_k + d_{k+1}) + (zs_{k+1} x[z_ch[k+1]] - zs_k x[z_ch[k]] + c_k),   d_k = T_k f_k - tb_k,
+ *           c_k = zb_{k+1} - zb_k + hl_k (tb_k + tb_{k+1})
+ *     out[n][k] = sum_p quad[p] w[n][k][p] r_k(p)^2
+ * with wgt f32 or NULL (= 1), addressed as wgt + n w_sn + k w_sk + p (a stride of 0 broadcasts), quad (HW) f32.  2 <= K <=
+ * MK_CMIX_LEVELS; NQ = 0 (dry) or K.  The two DEVICE tables:
+ *     itab (MK_HYDRO_ITAB + NR int32): z_ch, t_ch, q_ch (MK_CMIX_LEVELS each; entries beyond K, and all of q_ch when NQ = 0, must
+ *         repeat a VALID channel: they are read, the value is dropped), then the NR = C - 2 K - NQ channels the loss does not read
+ *     ftab (MK_HYDRO_FTAB f32, MK_CMIX_LEVELS each): zs = scale_z / R_d, c (above, folded on the host in fp64: the biases, of the
+ *         size of Z / R_d and T, meet there and not in fp32; the kernel adds deviations to the imbalance of the mean state), ts, tb,
+ *         qs, qb, hl_k = 1/2 ln(p_{k+1} / p_k); zero beyond their count (c, hl: beyond K - 1).
+ * The channel indices are NOT checked (device memory): the caller guarantees that they are < C and pairwise distinct.
+ *   mk_hydro_chunks: the number of partial sums per (n, k).
+ *   mk_hydro_sums:   one launch over x writes ws (N (K - 1) mk_hydro_chunks(HW) f32), a second, tiny one adds the chunks in index
+ *                    order into out (N, K - 1) f32.  No atomics: repeats are bit-identical.  Nothing is read on the host.
+ *   mk_hydro_grad:   gx (N, C, HW) in the dtype of x from g (N, K - 1) f32 DEVICE memory: the z, t (and q) channels, ZERO on the NR
+ *                    others; every element of gx is written once, no memset beforehand.
+ * Four consecutive pixels per thread (one 16-byte f32 / 8-byte bf16 access per channel) when HW, w_sn and w_sk are multiples of 4
+ * and every tensor pointer is 16-byte aligned; one pixel per thread otherwise.
+ *
+ * The preparation pass, prd (B, E, n) members, tar (B, n), the input state at inp + b inp_stride (n elements each), all of ONE
+ * dtype f32 | bf16, n = C HW points per sample, 1 <= E <= 32 (forward):
+ *     MK_PREP_MEAN      mean (B, n)      = inv sum_e prd_e      (sequential fp32 sum over e, rounded once)
+ *     MK_PREP_MEMBER_T  prd_t (B, E, n)  = prd_e - inp
+ *     MK_PREP_MEAN_T    mean_t (B, n)    = inv sum_e prd_e - inp (from the unrounded mean)
+ *     MK_PREP_TAR_T     tar_t (B, n)     = tar - inp
+ * Only the outputs selected in `flags` are written (and only the inputs they need are read).
+ *   mk_loss_prep_bwd: g_prd (B, E, n) = g_prd_t + inv (g_mean + g_mean_t); each of the three may be NULL (absent terms are skipped). */
+#define MK_HYDRO_ITAB (3 * MK_CMIX_LEVELS)
+#define MK_HYDRO_FTAB (7 * MK_CMIX_LEVELS)
+#define MK_PREP_MEAN 1
+#define MK_PREP_MEMBER_T 2
+#define MK_PREP_MEAN_T 4
+#define MK_PREP_TAR_T 8
+int mk_hydro_chunks(long long HW);
+int mk_hydro_sums(const void* x, int dtype, const float* wgt, long long w_sn, long long w_sk, const float* quad, float* out, float* ws,
+                  const int* itab, const float* ftab, int N, int C, int K, int NQ, int NR, float eps, long long HW, void* stream);
+int mk_hydro_grad(const void* x, int dtype, const float* wgt, long long w_sn, long long w_sk, const float* quad, const float* g, void* gx,
+                  const int* itab, const float* ftab, int N, int C, int K, int NQ, int NR, float eps, long long HW, void* stream);
+int mk_loss_prep_fwd(const void* prd, const void* tar, const void* inp, long long inp_stride, int dtype, void* mean, void* prd_t, void* mean_t,
+                     void* tar_t, int flags, float inv, int B, int E, long long n, void* stream);
+int mk_loss_prep_bwd(const void* g_prd_t, const void* g_mean, const void* g_mean_t, void* g_prd, int dtype, float inv, int B, int E,
+                     long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ from .losses import CRPSLoss, GradientCRPSLoss, VortDivCRPSLoss, GeometricLpLoss
 from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss, SpectralL2EnergyScoreLoss
 from .losses import SpectralAMSELoss, EnsembleNLLLoss, GaussianMMDLoss
 from .losses import SpectralCoherenceLoss, CoherenceRegularization, SpectralRegularization, EnsembleGramFn
+from .losses import HydrostaticBalanceLoss, DriftRegularization, LossHandler
 from .metrics import (GeometricL1, GeometricRMSE, GeometricACC, GeometricSpread, GeometricSSR, GeometricCRPS, GeometricRankHistogram,
                       deterministic_sums)
 from .stepper import MultiStepWrapper, SingleStepWrapper
@@ -30,6 +31,7 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
            "SpectralAMSELoss", "EnsembleNLLLoss", "GaussianMMDLoss",
            "SpectralCoherenceLoss", "CoherenceRegularization", "SpectralRegularization", "EnsembleGramFn",
+           "HydrostaticBalanceLoss", "DriftRegularization", "LossHandler",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
            "deterministic_sums",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",

@@ -8,7 +8,9 @@ The elementwise chain ``|prd - tar|^p * wgt * q`` and the plane reduction are ON
 dtypes (bf16 prediction, fp32 target) without a cast pass.  Spatially distributed quadrature sums over the
 "spatial" group of ``makani_amd.distributed``.
 """
+import contextlib
 import math
+from functools import partial
 from typing import List, Optional, Tuple
 
 import torch
@@ -16,6 +18,7 @@ import torch.nn as nn
 
 from . import _lib, legendre
 from ._lib import device_guard, check, dtype_code, lib, need_gpu, prep, ptr, stream
+from .constraints import MAX_LEVELS as MAX_HYDRO_LEVELS, Q_CORRECTION_MOIST_AIR, R_DRY_AIR, _Tabled, get_matching_channels_pl
 from .ensemble import MAX_ENSEMBLE          # noqa: F401  (importable from here as before)
 from .ensemble import (ReduceFromGroupFn, check_forecast_dims, check_weight_dims, ensemble_active, ensemble_size_check,
                        ensemble_split, flatten_and_split)
@@ -212,6 +215,13 @@ class SpectralLpLoss(nn.Module):
         self.p, self.relative, self.squared, self.eps = p, relative, squared, eps
 
     @property
+    def type(self):
+        return "deterministic"                                                  # LossType.Deterministic
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
+
+    @property
     def n_channels(self):
         return len(self.channel_names)
 
@@ -307,6 +317,13 @@ class GeometricLpLoss(nn.Module):
                                          crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
         self.spatial_distributed = self.quadrature.distributed
         self.p, self.relative, self.squared, self.eps = p, relative, squared, eps
+
+    @property
+    def type(self):
+        return "deterministic"                                                  # LossType.Deterministic
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
 
     @property
     def n_channels(self):
@@ -551,6 +568,10 @@ class SpectralCRPSLoss(SpectralLpLoss):
         self.register_buffer("ensemble_weights", None if ensemble_weights is None else ensemble_weights.float().reshape(-1).contiguous(),
                              persistent=False)
 
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
     @torch.compiler.disable(recursive=True)
     @device_guard
     def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spectral_weights: Optional[torch.Tensor] = None,
@@ -605,6 +626,22 @@ def get_wind_channels(channel_names):
 _SURFACE_01 = ("u10m", "v10m", "u100m", "v100m", "tp", "sp", "msl", "tcwv", "sst")
 
 
+_HANDLER_WEIGHTS = False          # True while LossHandler asks a loss for its weights (``_handler_weights``)
+
+
+@contextlib.contextmanager
+def _handler_weights():
+    """Inside, ``channel_weighting`` returns what the reference's helper returns: the weights divided by their sum and multiplied
+    by the time-difference scale.  Outside (a loss asked directly) the weights stay as this project has always returned them:
+    not normalised, a time-difference scale an error."""
+    global _HANDLER_WEIGHTS
+    before, _HANDLER_WEIGHTS = _HANDLER_WEIGHTS, True
+    try:
+        yield
+    finally:
+        _HANDLER_WEIGHTS = before
+
+
 def channel_weighting(channel_names, channel_weight_type, time_diff_scale=None):
     """the "constant", "auto" and "new auto" rules of ``base_loss.py:33-72`` (pressure-level channels weighted by their level);
     the tabulated "custom" weights and the time-difference scalings are not carried here"""
@@ -622,6 +659,9 @@ def channel_weighting(channel_names, channel_weight_type, time_diff_scale=None):
                 w[c] = 0.01
     elif channel_weight_type != "constant":
         raise NotImplementedError(f"channel weighting {channel_weight_type!r} is not built on the HIP path (constant, auto, new auto)")
+    if _HANDLER_WEIGHTS:          # LossHandler asks: normalised, times the time-difference scale (base_loss.py:233-240)
+        w = w / torch.sum(w)
+        return w if time_diff_scale is None else w * time_diff_scale
     if time_diff_scale is not None:
         raise NotImplementedError("time-difference scaling of the channel weights is not built on the HIP path")
     return w
@@ -966,6 +1006,10 @@ class _SpectralEnergyScore(_EnergyScoreMixin, SpectralLpLoss):
     type = _EnsembleLoss.type                                                   # (the rest of that base belongs to the grid)
 
     _ensemble_split_lm = staticmethod(_ensemble_split_lm)          # (shared with the coherence losses below)
+
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
 
     def _score(self, forecasts, observations, per_degree):
         from . import comm as _comm
@@ -1326,6 +1370,10 @@ class _EnsembleGramLoss(SpectralLpLoss):
 
     type = _EnsembleLoss.type
 
+    @property
+    def type(self):
+        return "probabilistic"                                                  # LossType.Probabilistic
+
     def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
         return channel_weighting(self.channel_names, channel_weight_type, time_diff_scale)
 
@@ -1517,3 +1565,434 @@ class SpectralRegularization(_EnsembleGramLoss):
             from . import comm as _comm
             diff = ReduceFromGroupFn.apply(diff, _comm.get_group("ensemble")) / float(_comm.get_size("ensemble"))
         return self._sum_degrees(diff) / float(self.sht.lmax)
+
+
+# --------------------------------------------------------------------------- #
+# hydrostatic-balance loss (makani/utils/losses/hydrostatic_loss.py) and drift regularization (regularization.py:31-81)
+# --------------------------------------------------------------------------- #
+class HydrostaticBalanceLoss(_Tabled):
+    """``HydrostaticBalanceLoss`` of ``makani/utils/losses/hydrostatic_loss.py`` ("hydrostatic"): per interval of neighbouring
+    pressure levels the quadrature of the squared residual ``(Z_{k+1} - Z_k) / R_d + 1/2 ln(p_{k+1} / p_k) (T_k + T_{k+1})`` of the
+    de-normalised prediction (virtual temperature with ``use_moist_air_formula``), ``forward(prd (B, C, H, W), tar, wgt=None) ->
+    (B, K - 1)`` in the dtype of ``prd``.  Constructor arguments, the non-persistent buffers ``bias``, ``scale``, ``p`` and ``cmat``
+    (built by the reference's own fp32 steps, logarithms included) and both errors are the reference's.  The forward is ONE launch
+    over the prediction, f32 or bf16 in place (``csrc/hydro.hip``: de-normalisation, residuals, weights and plane sums; a second,
+    tiny launch adds the chunk sums in order), the backward one launch that writes the gradient of every channel.  Stated
+    deviations: at most ``MAX_LEVELS`` = 16 levels (the column lives in registers; the reference has no limit); a prediction with
+    ``(n_future + 1) C`` channels, on which the reference raises, is scored step by step -> ``(B, S (K - 1))``, step-major;
+    ``compute_channel_weighting`` accepts the ``time_diff_scale`` keyword that ``LossHandler`` passes (the reference's method lacks
+    it and dies with a ``TypeError`` there) and raises ``NotImplementedError`` for a value other than ``None``."""
+
+    _table_sources = ("bias", "scale", "cmat")
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, bias: torch.Tensor, scale: torch.Tensor, p_min: Optional[int] = 0,
+                 p_max: Optional[int] = 1000, use_moist_air_formula: Optional[bool] = False,
+                 spatial_distributed: Optional[bool] = False, **kwargs):
+        super().__init__()
+        self.img_shape, self.crop_shape, self.crop_offset = img_shape, crop_shape, crop_offset
+        self.channel_names = channel_names
+        self.quadrature = GridQuadrature(grid_to_quadrature_rule(grid_type), img_shape=img_shape, crop_shape=crop_shape,
+                                         crop_offset=crop_offset, normalize=True, distributed=spatial_distributed)
+        self.spatial_distributed = self.quadrature.distributed
+        self.use_moist_air_formula = use_moist_air_formula
+        self.z_idx, self.t_idx, self.pressures = get_matching_channels_pl(channel_names, "z", "t", p_min, p_max)
+        if self.use_moist_air_formula:
+            self.q_idx, _, p_tmp = get_matching_channels_pl(channel_names, "q", "t", p_min, p_max)
+        if len(self.pressures) < 2:
+            raise ValueError("Warning, we could not find at least two pressure levels which are common among z and t and inside "
+                             "the specified limits")
+        if self.use_moist_air_formula:
+            for p1, p2 in zip(self.pressures, p_tmp):
+                if p1 != p2:
+                    raise ValueError("Error, make sure that you have the same pressure levels for t,z and q channels")
+            if len(self.q_idx) != len(self.pressures):          # (a q column shorter than z / t: the reference fails in forward)
+                raise ValueError("Error, make sure that you have the same pressure levels for t,z and q channels")
+        K = len(self.pressures)
+        if K > MAX_HYDRO_LEVELS:
+            raise ValueError(f"Error, {K} pressure levels: the HIP path keeps a column of at most {MAX_HYDRO_LEVELS} levels in registers.")
+        self.register_buffer("bias", bias, persistent=False)
+        self.register_buffer("scale", scale, persistent=False)
+        self.prefact = 1.0 / R_DRY_AIR
+        if self.use_moist_air_formula:
+            self.q_prefact = Q_CORRECTION_MOIST_AIR
+        ptens = torch.as_tensor(self.pressures, dtype=torch.float32).reshape(1, -1, 1, 1)
+        self.register_buffer("p", ptens, persistent=False)
+        # one equation per interval; every factor by the reference's fp32 steps (a 0-dim quotient, its logarithm, times 0.5)
+        cmat = torch.zeros((K - 1, len(channel_names)), dtype=torch.float32)
+        for k in range(K - 1):
+            half_log = 0.5 * torch.log(ptens[0, k + 1, 0, 0] / ptens[0, k, 0, 0])
+            cmat[k, self.z_idx[k]] = -self.prefact
+            cmat[k, self.z_idx[k + 1]] = self.prefact
+            cmat[k, self.t_idx[k]] = half_log
+            cmat[k, self.t_idx[k + 1]] = half_log
+        self.register_buffer("cmat", cmat, persistent=False)
+
+    @property
+    def type(self):
+        return "deterministic"                                                  # LossType.Deterministic
+
+    @property
+    def n_channels(self):
+        return self.cmat.shape[0]
+
+    def compute_channel_weighting(self, channel_weight_type: str, time_diff_scale: torch.Tensor = None) -> torch.Tensor:
+        channel_weights = torch.ones(self.n_channels, dtype=torch.float32)
+        if not channel_weight_type == "constant":
+            raise NotImplementedError(f"Error, channel_weight_type {channel_weight_type} not supported for hydrostatic loss")
+        if time_diff_scale is not None:
+            raise NotImplementedError("Error, a time-difference scale is per channel; the hydrostatic loss has one entry per level interval")
+        return channel_weights / torch.sum(channel_weights)
+
+    def _build_tables(self, device):
+        from . import ops
+        K, C = len(self.pressures), len(self.channel_names)
+        cm = self.cmat.detach().cpu()
+        half_log = torch.stack([cm[k, self.t_idx[k]] for k in range(K - 1)])
+        return ops.hydro_table(self.z_idx, self.t_idx, self.q_idx if self.use_moist_air_formula else [], C, self.bias.expand(1, C, 1, 1),
+                               self.scale.expand(1, C, 1, 1), half_log, float(cm[0, self.z_idx[1]]),
+                               Q_CORRECTION_MOIST_AIR if self.use_moist_air_formula else 0.0, device)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, prd: torch.Tensor, tar: torch.Tensor = None, wgt: Optional[torch.Tensor] = None, **kwargs) -> torch.Tensor:
+        from . import ops
+        need_gpu(prd)
+        C = len(self.channel_names)
+        if prd.dim() != 4 or prd.shape[1] % C:
+            raise ValueError(f"Error, the hydrostatic loss expects (B, S * {C}, H, W) predictions, got {tuple(prd.shape)}")
+        q = self.quadrature.quad_weight.reshape(-1)
+        if q.numel() != prd.shape[-2] * prd.shape[-1]:
+            raise ValueError(f"Error, the prediction's plane {tuple(prd.shape[-2:])} is not the quadrature's {tuple(self.quadrature.quad_weight.shape[-2:])}")
+        sums = ops.HydroSumsFn.apply(prd, wgt, q, self._tables(prd.device), prd.shape[1] // C)
+        return self.quadrature._reduce(sums).to(prd.dtype)
+
+
+class DriftRegularization(_EnsembleLoss):
+    """``DriftRegularization`` of ``makani/utils/losses/regularization.py:31-81`` ("drift_regularization"): ``|quadrature(prd) -
+    quadrature(tar)|^p`` per channel, the mean over the members of a 5-D prediction (summed over the "ensemble" group and divided
+    by its size with ``ensemble_distributed``) -> (B, C).  The two quadratures are the plane-sum kernel of ``GridQuadrature``."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], p: Optional[float] = 1.0, grid_type: Optional[str] = "equiangular",
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
+        self.p = p
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, prd: torch.Tensor, tar: torch.Tensor, wgt: Optional[torch.Tensor] = None, **kwargs):
+        need_gpu(prd)
+        if prd.dim() > tar.dim():
+            tar = tar.unsqueeze(1)
+        loss = torch.abs(self.quadrature(prd) - self.quadrature(tar)).pow(self.p)
+        if prd.dim() == 5:
+            loss = torch.mean(loss, dim=1)
+            if self.ensemble_distributed:
+                from . import comm as _comm
+                loss = ReduceFromGroupFn.apply(loss, _comm.get_group("ensemble")) / float(_comm.get_size("ensemble"))
+        return loss
+
+
+# --------------------------------------------------------------------------- #
+# LossHandler (makani/utils/loss.py:57-494)
+# --------------------------------------------------------------------------- #
+_LOSS_REGISTRY = {
+    "l1": partial(GeometricLpLoss, p=1),
+    "l2": partial(GeometricLpLoss, p=2),
+    "spectral l1": partial(SpectralLpLoss, p=1),
+    "spectral l2": partial(SpectralLpLoss, p=2),
+    "h1": SpectralH1Loss,
+    "amse": SpectralAMSELoss,
+    "hydrostatic": HydrostaticBalanceLoss,
+    "ensemble_crps": CRPSLoss,
+    "ensemble_spectral_crps": SpectralCRPSLoss,
+    "ensemble_vort_div_crps": VortDivCRPSLoss,
+    "ensemble_gradient_crps": GradientCRPSLoss,
+    "ensemble_nll": EnsembleNLLLoss,
+    "gaussian_mmd": GaussianMMDLoss,
+    "lp_energy_score": LpEnergyScoreLoss,
+    "l2_energy_score": partial(LpEnergyScoreLoss, p=2.0),
+    "sobolev_energy_score": SobolevEnergyScoreLoss,
+    "spectral_l2_energy_score": SpectralL2EnergyScoreLoss,
+    "drift_regularization": DriftRegularization,
+    "spectral_regularization": SpectralRegularization,
+}
+
+
+def _params_get(params, key, default=None):
+    return params.get(key, default) if hasattr(params, "get") else getattr(params, key, default)
+
+
+class LossHandler(nn.Module):
+    """``LossHandler`` of ``makani/utils/loss.py:57-494``: builds the losses of ``params.losses`` (or ``params.loss``) from the
+    registry, owns their channel weights, relative weights, multistep weights and running statistics, and in ``forward(prd, tar,
+    wgt=None, inp=None, training_progress=None)`` hands every loss the tensors it scores — the ensemble mean for the deterministic
+    ones, tendencies against the last input step where a loss asks for them — and returns the weighted scalar.  Buffers, their
+    persistence and shapes are the reference's (a reference ``state_dict`` loads strictly), as are the per-loss keys
+    (``parameters``, ``channel_weights``, ``relative_weight``, ``temp_diff_normalization``, ``tendency``), the six multistep weight
+    types and every error.  The four tensors the reference forms in separate torch passes (``mean_E(prd)``, ``prd - inp``,
+    ``mean - inp``, ``tar - inp``) come from ONE launch that writes only what some loss reads (``ops.LossPrepFn``).
+
+    Under ``n_future > 0`` every loss returns step-major vectors ``[step 0: its channels | step 1: its channels | ..]`` and the
+    handler concatenates them per LOSS, while the weights are the per-loss weights concatenated and then tiled per STEP
+    (``loss.py:457,488``): with more than one loss the two orders differ, and a weight can meet another loss's value.  This is
+    reproduced as it is (the recorded reference values pin it), not repaired.
+
+    Stated deviations: ``bias``, ``scale`` (1, C, 1, 1) and ``time_diff_stds`` (C) are tensors of the OUTPUT channels (the reference
+    reads the files named in ``params``); ``compile`` is accepted and ignored; ``random_slice_loss=True`` raises
+    ``NotImplementedError`` (a C x C channel mix; this project ships no library GEMM); ``uncertainty_weighting`` /
+    ``balanced_weighting`` choose "ones until 100 batches" with ``torch.where`` on the device counter (the reference reads it with
+    ``.item()``); ``randomized_loss_weights`` draws from a device ``torch.Generator`` seeded with ``seed``; a tendency needs as many
+    input as prediction channels at any ``n_future`` (the reference checks at ``n_future = 0`` and fails in the subtraction
+    otherwise); CPU tensors raise.  Except for the randomized draw nothing is read on the host: forward and backward replay from a
+    captured graph."""
+
+    def __init__(self, params, track_running_stats: bool = False, seed: int = 0, eps: float = 1e-6, compile: bool = True, *,
+                 bias: Optional[torch.Tensor] = None, scale: Optional[torch.Tensor] = None,
+                 time_diff_stds: Optional[torch.Tensor] = None, **kwargs):
+        super().__init__()
+        from . import comm as _comm
+        _comm.autodetect()
+        self.rank = _comm.get_rank("matmul")
+        self.n_future = params.n_future
+        self.n_history = params.n_history
+        self.spatial_distributed = _comm.is_distributed("spatial") and (_comm.get_size("spatial") > 1)
+        self.ensemble_distributed = _comm.is_distributed("ensemble") and (_comm.get_size("ensemble") > 1)
+        self.img_shape = (params.img_shape_x_resampled, params.img_shape_y_resampled)
+        self.crop_shape = (params.img_shape_x_resampled, params.img_shape_y_resampled)
+        self.crop_offset = (params.img_crop_offset_x, params.img_crop_offset_y)
+        self.uncertainty_weighting = _params_get(params, "uncertainty_weighting", False)
+        self.balanced_weighting = _params_get(params, "balanced_weighting", False)
+        self.randomized_loss_weights = _params_get(params, "randomized_loss_weights", False)
+        self.random_slice_loss = _params_get(params, "random_slice_loss", False)
+        if self.random_slice_loss:
+            raise NotImplementedError("random_slice_loss mixes the channels with a C x C matrix per call; it is not built on the HIP path")
+        self.track_running_stats = track_running_stats or self.uncertainty_weighting or self.balanced_weighting
+        self.eps = eps
+        self.seed = seed
+
+        if hasattr(params, "losses"):
+            losses = params.losses
+        elif hasattr(params, "loss"):
+            losses = [{"type": params.loss}]
+        else:
+            raise ValueError("No loss function specified.")
+
+        n_out = len(params.channel_names)
+        bias = torch.zeros((1, n_out, 1, 1), dtype=torch.float32) if bias is None else torch.as_tensor(bias).detach().to(torch.float32).cpu()
+        scale = torch.ones((1, n_out, 1, 1), dtype=torch.float32) if scale is None else torch.as_tensor(scale).detach().to(torch.float32).cpu()
+
+        self.loss_fn = nn.ModuleList([])
+        self.loss_requires_input = []
+        self.loss_types = []
+        channel_weights = []
+        for loss in losses:
+            requires_input = loss.get("tendency", False)
+            loss_params = loss.get("parameters", {})
+            loss_handle = self._parse_loss_type(loss["type"])
+            loss_fn = loss_handle(img_shape=self.img_shape, crop_shape=self.crop_shape, crop_offset=self.crop_offset,
+                                  channel_names=params.channel_names, bias=bias, scale=scale, grid_type=params.model_grid_type,
+                                  spatial_distributed=self.spatial_distributed, ensemble_distributed=self.ensemble_distributed,
+                                  **loss_params)
+            self.loss_types.append(loss_fn.type)
+            self.loss_fn.append(loss_fn)
+            self.loss_requires_input.append(requires_input)
+
+            channel_weight_type = loss["channel_weights"] if "channel_weights" in loss.keys() else "constant"
+            if loss.get("temp_diff_normalization", False):
+                if time_diff_stds is None:
+                    raise ValueError("time_diff_std_path not defined.")          # (here: the time_diff_stds tensor was not given)
+                tds = torch.clamp(torch.as_tensor(time_diff_stds).detach().to(torch.float32).cpu().flatten(), min=1e-4)
+                time_diff_scale = scale.flatten() / tds
+            else:
+                time_diff_scale = None
+            if isinstance(channel_weight_type, list):
+                chw = torch.tensor(channel_weight_type, dtype=torch.float32)
+                if time_diff_scale is not None:
+                    chw = chw * time_diff_scale
+                if chw.shape[1] != loss_fn.n_channels:
+                    raise ValueError(f"expected channel weights to have {loss_fn.n_channels} channels, but got {chw.shape[1]}")
+            else:
+                with _handler_weights():
+                    chw = loss_fn.compute_channel_weighting(channel_weight_type, time_diff_scale=time_diff_scale)
+                chw = torch.as_tensor(chw, dtype=torch.float32)
+            chw = chw.reshape(1, -1).clone()
+            if "relative_weight" in loss.keys():
+                chw *= loss["relative_weight"]
+            channel_weights.append(chw)
+
+        channel_weights = torch.cat(channel_weights, dim=1)
+        ncw = channel_weights.shape[1]
+        self.register_buffer("channel_weights", channel_weights, persistent=False)
+        stats_buffer_shape = (self.n_future + 1) * channel_weights.shape[-1]
+        self.register_buffer("running_mean", torch.zeros(stats_buffer_shape), persistent=True)
+        self.register_buffer("running_var", torch.ones(stats_buffer_shape), persistent=True)
+        self.register_buffer("num_batches_tracked", torch.tensor([0], dtype=torch.long), persistent=True)
+        multistep_params = _params_get(params, "multistep", {"weight_type": "constant"})
+        multistep_weight = self._compute_multistep_weight(**multistep_params)
+        # (the step weight is the slow index, the channel the fast one)
+        multistep_weight = torch.repeat_interleave(multistep_weight.reshape(1, -1), ncw, dim=1)
+        self.register_buffer("multistep_weight", multistep_weight, persistent=False)
+        self._rng = None
+
+    def _compute_multistep_weight(self, **kwargs) -> torch.Tensor:
+        weight_type = kwargs.get("weight_type", "constant")
+        n = self.n_future + 1
+        if weight_type == "constant":
+            w = torch.ones(n, dtype=torch.float32) / float(n)
+        elif weight_type == "balanced":          # the n-th step is back-propagated n times
+            w = 2.0 * torch.arange(1, n + 1, dtype=torch.float32) / float((n + 1) * n)
+        elif weight_type == "linear":
+            w = torch.arange(1, n + 1, dtype=torch.float32) / float(n)
+        elif weight_type == "last-n-1":
+            w = torch.ones(n, dtype=torch.float32) / float(self.n_future)
+            w[0] = 0.0
+        elif weight_type == "last":
+            w = torch.zeros(n, dtype=torch.float32)
+            w[-1] = 1.0
+        elif weight_type == "custom":
+            w = torch.as_tensor(kwargs["weights"], dtype=torch.float32)
+            if w.shape[0] != n:
+                raise ValueError(f"Number of multistep weights ({w.shape[0]}) must match n_future+1 ({n})")
+        else:
+            raise ValueError(f"Unknown multistep loss weight type: {weight_type}")
+        return w
+
+    def _parse_loss_type(self, loss_type: str):
+        if loss_type not in _LOSS_REGISTRY:
+            raise NotImplementedError(f"Unknown loss function: {loss_type}")
+        return _LOSS_REGISTRY[loss_type]
+
+    def _gather_batch(self, x: torch.Tensor) -> torch.Tensor:
+        from . import comm as _comm
+        if _comm.is_distributed("batch") and _comm.get_size("batch") > 1:
+            from . import ops
+            n, me = _comm.get_size("batch"), _comm.get_rank("batch")
+            parts = torch.zeros((n, *x.shape), dtype=x.dtype, device=x.device)          # every rank fills its own rows, the sum gathers
+            parts[me] = x
+            ops._all_reduce_sum(parts, _comm.get_group("batch"))
+            x = parts.reshape(n * x.shape[0], *x.shape[1:])
+        return x
+
+    def is_distributed(self):
+        return False
+
+    def _update_running_stats(self, x: torch.Tensor):
+        """Chan, Golub and LeVeque's parallel update of mean and second moment with the batch's"""
+        with torch.no_grad():
+            num_batches = torch.ones_like(x[:, 0], dtype=torch.long)
+            num_batches = self._gather_batch(num_batches).sum()
+            x = self._gather_batch(x)
+            var, mean = torch.var_mean(x, dim=(0), correction=0, keepdim=False)
+            m2 = var * num_batches
+            delta = mean - self.running_mean
+            self.running_var += m2 + delta**2 * self.num_batches_tracked * num_batches / (self.num_batches_tracked + num_batches)
+            self.running_mean += delta * num_batches / (self.num_batches_tracked + num_batches)
+            self.num_batches_tracked += num_batches
+
+    def get_running_stats(self, correction: int = 0):
+        if not self.track_running_stats:
+            raise ValueError("Module does not track running stats")
+        var = self.running_var / (self.num_batches_tracked - int(correction))
+        return var, self.running_mean
+
+    def reset_running_stats(self):
+        with torch.no_grad():
+            self.running_mean.zero_()
+            self.running_var.fill_(1)
+            self.num_batches_tracked.zero_()
+
+    def _extract_input_state(self, inp: torch.Tensor) -> torch.Tensor:
+        """the last step of a flattened history (B, (n_history + 1) C, H, W) -> (B, C, H, W), a view"""
+        n_channels_per_step = inp.shape[1] // (self.n_history + 1)
+        return inp[..., -n_channels_per_step:, :, :]
+
+    def _prepare(self, prd, tar, inp):
+        """(prdm, prd_t, prdm_t, tar_t): the ensemble mean, the member / mean / target tendencies; what no loss reads is None"""
+        from . import comm as _comm
+        from . import ops
+        ens = prd.dim() == 5
+        tend = inp is not None and any(self.loss_requires_input)
+        uses = set(zip(self.loss_types, (bool(r) and tend for r in self.loss_requires_input)))
+        inp_state = None
+        if tend:
+            inp_state = self._extract_input_state(inp)
+            if prd.shape[-3] != inp_state.shape[1]:
+                raise ValueError(f"Channel mismatch: prediction has {prd.shape[-3]} channels but input has {inp_state.shape[1]} channels")
+        flags = 0
+        if ens and ("deterministic", False) in uses:
+            flags |= ops.PREP_MEAN
+        if ("deterministic", True) in uses or (not ens and ("probabilistic", True) in uses):
+            flags |= ops.PREP_MEAN_T
+        if ens and ("probabilistic", True) in uses:
+            flags |= ops.PREP_MEMBER_T
+        if tend:
+            flags |= ops.PREP_TAR_T
+        if flags == 0:
+            return prd, None, None, None
+        p5 = prd if ens else prd.unsqueeze(1)
+        E = p5.shape[1]
+        if ens and self.ensemble_distributed:          # the local sum over 1 / (E_loc * group size), summed over the group (loss.py:395-397)
+            group, gsize = _comm.get_group("ensemble"), _comm.get_size("ensemble")
+            first = (flags & ~ops.PREP_MEAN_T) | (ops.PREP_MEAN if flags & (ops.PREP_MEAN | ops.PREP_MEAN_T) else 0)
+            prdm, prd_t, _, tar_t = ops.LossPrepFn.apply(p5, tar, inp_state, first, 1.0 / float(E * gsize))
+            prdm_t = None
+            if prdm is not None:
+                prdm = ReduceFromGroupFn.apply(prdm, group)
+                if flags & ops.PREP_MEAN_T:
+                    prdm_t = ops.LossPrepFn.apply(prdm.unsqueeze(1), tar, inp_state, ops.PREP_MEAN_T, 1.0)[2]
+            return prdm, prd_t, prdm_t, tar_t
+        prdm, prd_t, prdm_t, tar_t = ops.LossPrepFn.apply(p5, tar, inp_state, flags, 1.0 / float(E))
+        if not ens:
+            prdm, prd_t = prd, prdm_t
+        return prdm, prd_t, prdm_t, tar_t
+
+    @device_guard
+    def forward(self, prd: torch.Tensor, tar: torch.Tensor, wgt: Optional[torch.Tensor] = None, inp: Optional[torch.Tensor] = None,
+                training_progress: Optional[float] = None, **kwargs):
+        # prd (B, E, C, H, W) or (B, C, H, W)
+        need_gpu(prd)
+        prdm, prd_t, prdm_t, tar_t = self._prepare(prd, tar, inp)
+        tend = tar_t is not None
+        loss_vals = []
+        for lfn, requires_inp, loss_type in zip(self.loss_fn, self.loss_requires_input, self.loss_types):
+            if self.n_future > 0:
+                lead_time_step = torch.arange(0, self.n_future + 1, dtype=torch.long, device=prd.device).repeat_interleave(lfn.n_channels)
+            else:
+                lead_time_step = None
+            kwargs_step = {"lead_time_step": lead_time_step, "training_progress": training_progress, "n_future": self.n_future}
+            if loss_type == "deterministic":
+                a, b = (prdm_t, tar_t) if (requires_inp and tend) else (prdm, tar)
+            else:
+                a, b = (prd_t, tar_t) if (requires_inp and tend) else (prd, tar)
+            loss_vals.append(lfn(a, b, wgt, **kwargs_step))
+        all_losses = torch.cat(loss_vals, dim=-1)
+
+        if self.training and self.track_running_stats:
+            self._update_running_stats(all_losses.clone())
+
+        chw = self.channel_weights
+        if self.uncertainty_weighting and self.training:
+            var, _ = self.get_running_stats()
+            var = torch.where(self.num_batches_tracked <= 100, torch.ones_like(var), var)
+            chw = chw / (torch.sqrt(2 * var) + self.eps)
+        elif self.balanced_weighting and self.training:
+            _, mean = self.get_running_stats()
+            mean = torch.where(self.num_batches_tracked <= 100, torch.ones_like(mean), mean)
+            chw = chw / (mean + self.eps)
+
+        if self.randomized_loss_weights:
+            if self._rng is None or self._rng.device != chw.device:
+                self._rng = torch.Generator(device=chw.device)
+                self._rng.manual_seed(self.seed)
+            rmask = torch.zeros_like(chw)
+            rmask.uniform_(0.0, 1.0, generator=self._rng)
+            chw = chw * (rmask / rmask.sum())
+
+        if self.training:
+            if self.n_future > 0:          # the per-loss weights, concatenated, tiled per step: see the class docstring
+                chw = torch.tile(chw, (1, self.n_future + 1))
+            chw = chw * self.multistep_weight
+
+        return torch.mean(torch.sum(chw * all_losses, dim=1), dim=0)

@@ -1957,3 +1957,157 @@ class SiStepFn(torch.autograd.Function):
         gx0, gx, gb = si_step_bwd(g, coef, C_, last, (need[2], need[0], need[1]), dts)
         gx0, gx, gb = (t if t is None or t.dtype == o else t.to(o) for t, o in zip((gx0, gx, gb), orig))
         return gx, gb, gx0, None, None, None, None, None, None, None, None
+
+
+# ---- hydrostatic-balance loss and the loss handler's preparation pass (csrc/hydro.hip) ------------------------------------------
+HYDRO_LEVELS = CMIX_LEVELS
+PREP_MEAN, PREP_MEMBER_T, PREP_MEAN_T, PREP_TAR_T = (_lib.CONSTS["MK_PREP_" + k] for k in ("MEAN", "MEMBER_T", "MEAN_T", "TAR_T"))
+
+
+@dataclass
+class HydroTable:
+    """The descriptor of ``mk_hydro_sums`` / ``mk_hydro_grad`` (the layout of the two device tables is in include/makani_amd.h)"""
+    itab: torch.Tensor
+    ftab: torch.Tensor
+    C: int
+    K: int
+    NQ: int
+    NR: int
+    eps: float
+
+    def args(self):
+        return (self.C, self.K, self.NQ, self.NR, self.eps)
+
+
+def hydro_table(z_idx, t_idx, q_idx, C_, bias, scale, half_log, inv_rd, eps, device) -> HydroTable:
+    """``bias`` / ``scale`` (C) fp32 statistics, ``half_log`` (K - 1) the fp32 factors 1/2 ln(p_{k+1} / p_k) and ``inv_rd`` the fp32
+    value of 1 / R_d, as the loss's ``cmat`` holds them; folded in fp64 here, rounded once into the table.  The channel lists are
+    checked here (the kernels do not check them)."""
+    K, NQ = len(z_idx), len(q_idx)
+    if not 2 <= K <= HYDRO_LEVELS:
+        raise ValueError(f"Error, {K} pressure levels: the HIP path keeps a column of 2 .. {HYDRO_LEVELS} levels in registers.")
+    used = [*z_idx, *t_idx, *q_idx]
+    if len(t_idx) != K or NQ not in (0, K) or len(set(used)) != len(used) or min(used) < 0 or max(used) >= C_:
+        raise ValueError("the z, t and q channels of the hydrostatic loss must be distinct channels of the prediction, one per level")
+    rest = [c for c in range(C_) if c not in used]
+
+    def ipad(lst):
+        return list(lst) + [lst[-1] if lst else z_idx[0]] * (HYDRO_LEVELS - len(lst))
+
+    b64 = bias.detach().reshape(-1).to(device="cpu", dtype=torch.float64)
+    s64 = scale.detach().reshape(-1).to(device="cpu", dtype=torch.float64)
+    rd = float(inv_rd)
+    f = torch.zeros((7, HYDRO_LEVELS), dtype=torch.float64)
+    f[0, :K] = s64[z_idx] * rd
+    hl = half_log.detach().reshape(-1).to(device="cpu", dtype=torch.float64)
+    f[1, :K - 1] = (b64[z_idx[1:]] - b64[z_idx[:-1]]) * rd + hl * (b64[t_idx[:-1]] + b64[t_idx[1:]])
+    f[2, :K], f[3, :K] = s64[t_idx], b64[t_idx]
+    if NQ:
+        f[4, :K], f[5, :K] = s64[q_idx], b64[q_idx]
+    f[6, :K - 1] = hl
+    itab = torch.tensor(ipad(z_idx) + ipad(t_idx) + ipad(q_idx) + rest, dtype=torch.int32, device=device)
+    return HydroTable(itab, f.float().reshape(-1).to(device), C_, K, NQ, len(rest), float(eps) if NQ else 0.0)
+
+
+def _hydro_weight(wgt, N, K1, H, W, steps):
+    """the spatial weight as (tensor f32 | None, sample stride, interval stride): broadcast axes get the stride 0"""
+    if wgt is None:
+        return None, 0, 0
+    w = wgt.float()
+    if w.dim() != 4 or w.shape[-2:] != (H, W) or w.shape[1] not in (1, K1) or w.shape[0] not in (1, N // steps):
+        raise ValueError(f"the spatial weight {tuple(wgt.shape)} does not broadcast to the residuals ({N // steps}, {K1}, {H}, {W})")
+    if steps > 1 and (w.shape[0] > 1 or w.shape[1] > 1):          # (B, S (K - 1), H, W) -> one row per (b, s)
+        w = w.expand(N // steps, K1, H, W).reshape(N, K1 // steps, H, W)
+    w = w.contiguous()
+    hw = H * W
+    return w, (w.shape[1] * hw if w.shape[0] > 1 else 0), (hw if w.shape[1] > 1 else 0)
+
+
+class HydroSumsFn(torch.autograd.Function):
+    """``mk_hydro_sums`` / ``mk_hydro_grad``: x (B, S C, H, W) f32 | bf16 -> (B, S (K - 1)) f32, step-major; the gradient of every
+    channel of x in its dtype (zeros on the channels the loss does not read)"""
+
+    @staticmethod
+    def forward(ctx, x, wgt, quad, d, steps):
+        dtype_in = x.dtype
+        x = _planes(x, "losses")
+        B, SC, H, W = x.shape
+        if SC != steps * d.C:
+            raise ValueError(f"the hydrostatic loss expects {steps} x {d.C} channels, got {SC}")
+        if d.itab.device != x.device:
+            raise RuntimeError("the loss's tables live on another device than its input")
+        N, K1, hw = B * steps, d.K - 1, H * W
+        w, w_sn, w_sk = _hydro_weight(wgt, N, steps * K1, H, W, steps)
+        out = torch.empty((B, steps * K1), dtype=torch.float32, device=x.device)
+        ws = torch.empty((N * K1 * lib().mk_hydro_chunks(hw),), dtype=torch.float32, device=x.device)
+        check(lib().mk_hydro_sums(ptr(x), dtype_code(x), ptr(w), w_sn, w_sk, ptr(quad), ptr(out), ptr(ws), ptr(d.itab), ptr(d.ftab), N, *d.args(),
+                                  hw, stream()), "mk_hydro_sums")
+        ctx.save_for_backward(x, w, quad)
+        ctx.meta = (d, N, hw, w_sn, w_sk, dtype_in)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, quad = ctx.saved_tensors
+        d, N, hw, w_sn, w_sk, dtype_in = ctx.meta
+        g = g.float().contiguous()
+        gx = torch.empty_like(x)
+        check(lib().mk_hydro_grad(ptr(x), dtype_code(x), ptr(w), w_sn, w_sk, ptr(quad), ptr(g), ptr(gx), ptr(d.itab), ptr(d.ftab), N, *d.args(),
+                                  hw, stream()), "mk_hydro_grad")
+        return (gx if gx.dtype == dtype_in else gx.to(dtype_in)), None, None, None, None
+
+
+def loss_prep_launch(prd, tar, inp, flags, inv):
+    """``mk_loss_prep_fwd``: prd (B, E, C, H, W) f32 | bf16 contiguous, tar (B, C, H, W), inp (B, C, H, W) a view whose samples are
+    contiguous (the last step of a flattened history), both in the dtype of prd -> (mean, prd_t, mean_t, tar_t), None where unselected"""
+    B, E, C_, H, W = prd.shape
+    n = C_ * H * W
+    if E > 32:
+        raise NotImplementedError(f"ensemble size {E}: the HIP preparation pass keeps at most 32 members per point in registers")
+    tend = bool(flags & (PREP_MEMBER_T | PREP_MEAN_T | PREP_TAR_T))
+    stride = 0
+    if tend:
+        if inp.dtype != prd.dtype:
+            inp = inp.to(prd.dtype)
+        if not (inp[0].is_contiguous() and (B == 1 or inp.stride(0) >= n)):
+            inp = inp.contiguous()
+        stride = inp.stride(0) if B > 1 else n
+    if flags & PREP_TAR_T:
+        tar = tar.to(prd.dtype).contiguous()
+    new = lambda *s: torch.empty(s, dtype=prd.dtype, device=prd.device)          # noqa: E731
+    mean = new(B, C_, H, W) if flags & PREP_MEAN else None
+    prd_t = new(B, E, C_, H, W) if flags & PREP_MEMBER_T else None
+    mean_t = new(B, C_, H, W) if flags & PREP_MEAN_T else None
+    tar_t = new(B, C_, H, W) if flags & PREP_TAR_T else None
+    check(lib().mk_loss_prep_fwd(ptr(prd), ptr(tar) if flags & PREP_TAR_T else None, ptr(inp) if tend else None, stride, dtype_code(prd),
+                                 ptr(mean), ptr(prd_t), ptr(mean_t), ptr(tar_t), flags, float(inv), B, E, n, stream()), "mk_loss_prep_fwd")
+    return mean, prd_t, mean_t, tar_t
+
+
+class LossPrepFn(torch.autograd.Function):
+    """What ``LossHandler`` forms before any loss runs, in one launch: ``(mean, prd_t, mean_t, tar_t) = LossPrepFn.apply(prd, tar,
+    inp, flags, inv)`` with prd (B, E, C, H, W); outputs not selected in ``flags`` are None.  The gradient goes to ``prd`` alone
+    (target and input state are data): one launch, g_prd = g_prd_t + inv (g_mean + g_mean_t)."""
+
+    @staticmethod
+    def forward(ctx, prd, tar, inp, flags, inv):
+        _lib.need_gpu(prd, "losses")
+        dtype_in = prd.dtype
+        prd = _lib.prep(prd)
+        outs = loss_prep_launch(prd, tar, inp, flags, inv)
+        ctx.meta = (tuple(prd.shape), prd.dtype, dtype_in, float(inv))
+        if outs[3] is not None:
+            ctx.mark_non_differentiable(outs[3])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_mean, g_prd_t, g_mean_t, g_tar_t):
+        shape, dt, dtype_in, inv = ctx.meta
+        B, E = shape[:2]
+        n = int(np.prod(shape[2:]))
+        gs = [None if g is None else g.to(dt).contiguous() for g in (g_prd_t, g_mean, g_mean_t)]
+        if all(g is None for g in gs):
+            return None, None, None, None, None
+        g_prd = torch.empty(shape, dtype=dt, device=next(g for g in gs if g is not None).device)
+        check(lib().mk_loss_prep_bwd(ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(g_prd), dtype_code(g_prd), inv, B, E, n, stream()), "mk_loss_prep_bwd")
+        return (g_prd if dt == dtype_in else g_prd.to(dtype_in)), None, None, None, None

@@ -1,7 +1,7 @@
 """SHA-256 of every output of the kernels that share csrc/block_io.h, on fixed inputs at small shapes, from whichever library
 MAKANI_AMD_LIB names.  Two builds whose arithmetic and summation orders agree print the same lines:
        python tools/ab.py run parent new -- python tools/lib_digest.py
-   python tools/lib_digest.py [crps] [nll] [metrics] [escore] [egram] [preproc] [layernorm] [resample] [disco] [optim]
+   python tools/lib_digest.py [crps] [nll] [metrics] [escore] [egram] [preproc] [layernorm] [resample] [disco] [optim] [losshandler]
 Shapes: 33 x 40 points (a multiple of 4, two chunks of a plane) and 33 x 41 (odd: one element per thread), bases aligned and
 shifted by one element, both element types, ensembles of 2, 3, 5, 9 and 17 (every compiled capacity, each partly filled)."""
 import ctypes as C
@@ -223,7 +223,34 @@ def optim():
     emit("adamw_multi", p2, m2, v2)
 
 
+def losshandler():
+    B, C, K = 2, 9, 3                                           # z, t, q on three levels: channels 0 .. 8 in that order
+    ftab = torch.cat([rnd(16, pos=True) for _ in range(7)])
+    for n, shift in ((33 * 40, 0), (33 * 40, 1), (33 * 41, 0), (70 * 1024, 0)):          # the last: more points than 64 chunks of 1024
+        ch = lib().mk_hydro_chunks(n)
+        q, w, gout = rnd(n, pos=True) / n, rnd(B, K - 1, n, pos=True), rnd(B, K - 1)
+        for moist in (0, 1):
+            idx = [0, 1, 2] + [2] * 13 + [3, 4, 5] + [5] * 13 + ([6, 7, 8] + [8] * 13 if moist else [0] * 16) + ([] if moist else [6, 7, 8])
+            itab = torch.tensor(idx, dtype=torch.int32, device=dev)
+            for dt in (F32, BF16):
+                x = rnd(B, C, n, dt=dt, shift=shift)
+                out, ws, gx = torch.zeros(B, K - 1, device=dev), torch.zeros(B * (K - 1) * ch, device=dev), torch.zeros_like(x)
+                tail = (ptr(itab), ptr(ftab), B, C, K, K if moist else 0, 0 if moist else 3, 0.6078, n, stream())
+                check(lib().mk_hydro_sums(ptr(x), dtype_code(x), ptr(w), (K - 1) * n, n, ptr(q), ptr(out), ptr(ws), *tail))
+                check(lib().mk_hydro_grad(ptr(x), dtype_code(x), ptr(w), (K - 1) * n, n, ptr(q), ptr(gout), ptr(gx), *tail))
+                emit(f"hydro n={n} shift={shift} moist={moist} {tag(dt)}", out, gx)
+    for n, shift in ((2112, 0), (2112, 1), (2113, 0)):
+        for E in (1,) + ES + (32,):
+            for dt in (F32, BF16):
+                prd, tar, inp = rnd(B, E, n, dt=dt, shift=shift), rnd(B, n, dt=dt), rnd(B, n, dt=dt)
+                outs = [torch.zeros(B, n, dtype=dt, device=dev), torch.zeros_like(prd), torch.zeros(B, n, dtype=dt, device=dev), torch.zeros(B, n, dtype=dt, device=dev)]
+                check(lib().mk_loss_prep_fwd(ptr(prd), ptr(tar), ptr(inp), n, dtype_code(prd), *(ptr(o) for o in outs), 15, 1.0 / E, B, E, n, stream()))
+                g = torch.zeros_like(prd)
+                check(lib().mk_loss_prep_bwd(ptr(outs[1]), ptr(outs[0]), ptr(outs[2]), ptr(g), dtype_code(g), 1.0 / E, B, E, n, stream()))
+                emit(f"loss_prep n={n} shift={shift} E={E} {tag(dt)}", *outs, g)
+
+
 if __name__ == "__main__":
     print(f"library {_lib.LIB_PATH}", file=sys.stderr)
-    for fam in sys.argv[1:] or ["crps", "nll", "metrics", "escore", "egram", "preproc", "layernorm", "resample", "disco", "optim"]:
+    for fam in sys.argv[1:] or ["crps", "nll", "metrics", "escore", "egram", "preproc", "layernorm", "resample", "disco", "optim", "losshandler"]:
         globals()[fam]()

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -867,6 +867,78 @@ def interpolant():
                   f"{nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch sequence, {nops} compute ops, "
                   f"{tt:7.3f} ms = {nbytes / (tt * 1e-3) / 1e12:5.2f} TB/s of the same bytes = {tt / t:5.2f} x | max |kernel - torch| {err}",
                   flush=True)
+
+
+def losshandler():
+    """What LossHandler adds (csrc/hydro.hip) at (B, E, C, H, W) = (1, 16, 73, 721, 1440), bf16: the moist hydrostatic loss on 13
+    levels, forward + backward on the (1, 73, 721, 1440) ensemble mean, and the preparation launch with all four outputs (mean,
+    member tendencies, mean tendency, target tendency); each beside the same steps written in torch on the same tensors in the same
+    process (the reference's formulation: .float(), scale and bias, the moist correction, the matmul with cmat, square, quadrature,
+    backward by autograd; torch.mean and three subtractions), timed in turn over three rounds.  Algorithmic bytes: hydrostatic
+    one read of the 39 channels it uses per direction plus one write of all 73 in the backward; preparation one read of the members,
+    the target and the input state, one write of the four outputs."""
+    H, W, B, E = 721, 1440, 1, 16
+    N = H * W
+    levels = [50, 100, 150, 200, 250, 300, 400, 500, 600, 700, 850, 925, 1000]
+    names = ["u10m", "v10m", "u100m", "v100m", "t2m", "sp", "msl", "tcwv"] + [f"{v}{p}" for v in "uvztq" for p in levels]
+    C = len(names)
+    gen = torch.Generator().manual_seed(1)
+    bias, scale = torch.zeros(1, C, 1, 1), torch.ones(1, C, 1, 1)
+    for i, n in enumerate(names):
+        if n[1:].isdigit():
+            k = math.log(1000.0 / int(n[1:])) / math.log(20.0)
+            b, s = {"z": (600.0 + 6.9e4 * k, 3.0e3), "t": (285.0 - 70.0 * k, 15.0), "q": (2.0e-3, 2.0e-3), "u": (5.0, 10.0), "v": (0.0, 8.0)}[n[0]]
+            bias[0, i], scale[0, i] = b, s
+    PEAK, dt = 8.0e12, torch.bfloat16
+
+    def timed(fn):
+        once = max(timeit(fn, reps=3, warm=2), 1e-3)
+        return timeit(fn, reps=max(5, int(math.ceil(500.0 / once))), warm=1)
+
+    m = ma.HydrostaticBalanceLoss((H, W), (H, W), (0, 0), names, "equiangular", bias, scale, p_min=50, p_max=1000, use_moist_air_formula=True).to(dev)
+    x = torch.randn(B, C, H, W, generator=gen).to(dt).to(dev).requires_grad_(True)
+    g = torch.randn(B, len(levels) - 1, generator=gen).to(dev)
+    q = m.quadrature.quad_weight
+
+    def torch_hydro(x):
+        u = x.to(torch.float32) * m.scale + m.bias
+        u[:, m.t_idx] = u[:, m.t_idx] * (1.0 + m.q_prefact * u[:, m.q_idx])
+        r = torch.matmul(m.cmat, u.permute(1, 0, 2, 3).reshape(C, -1)).reshape(-1, B, H, W).permute(1, 0, 2, 3)
+        return torch.sum(torch.square(r) * q, dim=(-2, -1)).to(x.dtype)
+
+    ours = lambda: torch.autograd.grad(m(x, None), x, g.to(dt))[0]          # noqa: E731
+    composed = lambda: torch.autograd.grad(torch_hydro(x), x, g.to(dt))[0]          # noqa: E731
+    err = ((m(x, None).float() - torch_hydro(x).float()).abs().max().item() / torch_hydro(x).float().abs().max().item(),
+           (ours().float() - composed().float()).abs().max().item() / composed().float().abs().max().item())
+    nbytes = (2 * 39 + C) * B * N * 2
+    for rnd in range(3):
+        t, tt = timed(ours), timed(composed)
+        print(f"losshandler hydrostatic moist bf16 round {rnd}: forward + backward {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s = "
+              f"{nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch formulation {tt:7.3f} ms = {tt / t:5.2f} x | "
+              f"max |kernel - torch| / max {err[0]:.1e} {err[1]:.1e}", flush=True)
+    del x
+
+    prd = torch.randn(B, E, C, H, W, generator=gen).to(dt).to(dev)
+    tar, hist = torch.randn(B, C, H, W, generator=gen).to(dt).to(dev), torch.randn(B, 2 * C, H, W, generator=gen).to(dt).to(dev)
+    inp = hist[:, -C:]
+    flags = ops.PREP_MEAN | ops.PREP_MEMBER_T | ops.PREP_MEAN_T | ops.PREP_TAR_T
+
+    def ours_prep():
+        return ops.loss_prep_launch(prd, tar, inp, flags, 1.0 / E)
+
+    def torch_prep():
+        prdm = torch.mean(prd, dim=1)
+        return prdm, prd - inp.unsqueeze(1), prdm - inp, tar - inp
+
+    a, b = ours_prep(), torch_prep()
+    err = [(u.float() - v.float()).abs().max().item() for u, v in zip(a, b)]
+    del a, b
+    nbytes = ((E + 2) + (E + 3)) * B * C * N * 2
+    for rnd in range(3):
+        t, tt = timed(ours_prep), timed(torch_prep)
+        print(f"losshandler preparation E={E} bf16 all four outputs round {rnd}: {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s = "
+              f"{nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch (mean and three subtractions) {tt:7.3f} ms = "
+              f"{tt / t:5.2f} x | max |kernel - torch| {' '.join(f'{e:.1e}' for e in err)}", flush=True)
 
 
 if __name__ == "__main__":
