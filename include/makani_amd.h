@@ -528,6 +528,48 @@ int mk_metric_det_sums(const void* x, int x_dtype, const void* y, int y_dtype, c
 int mk_metric_ens_sums(const void* f, int f_dtype, const float* obs, const float* w, const float* q, float* out, float* ws, int B,
                        int E, int C, long long N, int which, void* stream);
 
+/* ---- a rollout step's validation metrics in one pass (makani/utils/metric.py:45-740: MetricsHandler.update) ----------------
+ * mk_mrollout_sums: every plane sum that any metric handle of a MetricsHandler needs, in ONE read of the selected planes.
+ *   pred (B, E, C, N) members f32 | bf16 read in place (E = 1: a deterministic prediction), tar (B, C, N) f32 | bf16,
+ *   w optional (B, C, N) f32, q (N), clim optional (Ja, N) f32.  table: DEVICE int32 (J, 3) = per plane {source channel in
+ *   0 .. C-1, MK_MROLL_* bits of the sums wanted from it, row of clim or -1}; a row outside these ranges yields zeros.
+ *   Per point: nan = isnan(t) (only when mask_nan), t' = nan ? 0 : t, w' = q w (nan ? 0 : 1), mu = the member mean in fp32
+ *   (mean first, centred on the first member).  partial[((b J + j) chunks + chunk) K + k], K = MK_MROLL_NSUM + E + 1,
+ *   chunks = mk_metric_chunks(N); every k is written (0 where not selected):
+ *     k = 0 sum w'   1 number of NaN points   2 sum w'|mu - t'|   3 sum w'(mu - t')^2   4, 5, 6 sum w'{x'y', x'^2, y'^2} with
+ *     x' = mu - clim, y' = t' - clim   7 sum w' sum_e (mu - f_e)^2   8 sum w' crps ("skillspread", alpha = 1; needs E >= 2)
+ *     9 + r  sum w' [r = #{e : f_e <= t'}], r = 0 .. E.
+ *   sums: optional (B, J, K); when given, a second launch adds the chunks of a plane in chunk order into it (what a spatially
+ *   split job all-reduces before the finish).  1 <= E <= 32, B * J <= 65535.
+ * mk_mrollout_finish: ONE launch for all nh handles.  sums (B, J, chunks, K) (chunks = 1 for the reduced sums): the chunks are
+ *   added in order, every handle's metric is formed per sample and summed over the batch, scaled, and merged into row idt of
+ *   its curve and counter in buf (curve += new; MK_MROLL_KIND_RMSE: sqrt(curve^2 + new^2); counter += counts).  counts = B
+ *   when has_weight == 0 and the handle's planes hold no NaN point in this batch, sum_b sums[.., 0] otherwise: decided here.
+ *   hdesc: DEVICE int32 (nh, MK_MROLL_HDESC) = {kind, channels n, offset into hplanes / hscale, offset of the curve in buf,
+ *   offset of the counter in buf, rollout steps}; hplanes: the plane j of every handle channel; hscale: its scale.
+ *   curve (steps, n) ((steps, n, E + 1) for MK_MROLL_KIND_HIST), counter (steps, n).  Writes outside [0, buf_len) are dropped. */
+#define MK_MROLL_L1 1
+#define MK_MROLL_L2 2
+#define MK_MROLL_ACC 4
+#define MK_MROLL_SPREAD 8
+#define MK_MROLL_CRPS 16
+#define MK_MROLL_HIST 32
+#define MK_MROLL_NSUM 9
+#define MK_MROLL_HDESC 6
+#define MK_MROLL_KIND_L1 0
+#define MK_MROLL_KIND_RMSE 1
+#define MK_MROLL_KIND_ACC 2
+#define MK_MROLL_KIND_CRPS 3
+#define MK_MROLL_KIND_SPREAD 4
+#define MK_MROLL_KIND_SSR 5
+#define MK_MROLL_KIND_HIST 6
+int mk_mrollout_sums(const void* pred, int p_dtype, const void* tar, int t_dtype, const float* w, const float* q, const float* clim,
+                     const int* table, float* partial, float* sums, int B, int E, int C, int J, int Ja, long long N, int mask_nan,
+                     void* stream);
+int mk_mrollout_finish(const float* sums, int chunks, const int* hdesc, const int* hplanes, const float* hscale, float* buf,
+                       long long buf_len, int nh, int B, int E, int J, int idt, int has_weight, float acc_eps, float ssr_eps,
+                       void* stream);
+
 /* ---- spectral noise processes on the sphere (makani/models/noise.py: BaseNoiseS2 / DiffusionNoiseS2 / DummyNoiseS2 update) ----
  * state: (B, T, C, L, M, 2) f32, updated in place in one pass (makani_amd/csrc/noise.hip).  s = reflect ? -1 : 1.
  *   MK_NOISE_WHITE:   state[:, t] = s xi[t]                                                     (T levels drawn)

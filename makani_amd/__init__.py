@@ -13,6 +13,7 @@ from .losses import SpectralCoherenceLoss, CoherenceRegularization, SpectralRegu
 from .losses import HydrostaticBalanceLoss, DriftRegularization, LossHandler
 from .metrics import (GeometricL1, GeometricRMSE, GeometricACC, GeometricSpread, GeometricSSR, GeometricCRPS, GeometricRankHistogram,
                       deterministic_sums)
+from .metric import MetricsHandler, MetricRollout, Quadrature, SimpsonQuadrature, TrapezoidQuadrature
 from .stepper import MultiStepWrapper, SingleStepWrapper
 from .disco import DiscreteContinuousConvS2, ResampleS2
 from .fcn3 import AtmoSphericNeuralOperatorNet
@@ -33,7 +34,7 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "SpectralCoherenceLoss", "CoherenceRegularization", "SpectralRegularization", "EnsembleGramFn",
            "HydrostaticBalanceLoss", "DriftRegularization", "LossHandler",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
-           "deterministic_sums",
+           "deterministic_sums", "MetricsHandler", "MetricRollout", "Quadrature", "SimpsonQuadrature", "TrapezoidQuadrature",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",
            "noise_seed_reflect", "Preprocessor2D",
            "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum",

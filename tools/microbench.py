@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -939,6 +939,55 @@ def losshandler():
         print(f"losshandler preparation E={E} bf16 all four outputs round {rnd}: {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s = "
               f"{nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch (mean and three subtractions) {tt:7.3f} ms = "
               f"{tt / t:5.2f} x | max |kernel - torch| {' '.join(f'{e:.1e}' for e in err)}", flush=True)
+
+
+def mhandler():
+    """One fused ``MetricsHandler.update`` (csrc/mrollout.hip: mk_mrollout_sums + mk_mrollout_finish) beside the composed
+    per-handle path (``use_fused = False``: the ensemble mean, a gathered copy per handle, the NaN test with its host read, one
+    metric pass per handle on csrc/metrics.hip and csrc/crps.hip, stack / combine / copy_) on the same GPU, in the same process,
+    the two timed in turn over three rounds.  Shapes: (1, 16, 73, 721, 1440) bf16 and (1, 1, 73, 721, 1440) f32 with the eight
+    default variables.  Each time as a share of the HBM roof for ITS OWN algorithmic traffic: fused = the (E + 1) * 8 selected
+    planes, the quadrature weights and ACC's climatology once; composed = the mean over all C channels (read E C planes, write
+    C fp32), and per handle the gathered copies of prediction and target (read + write), the NaN test (read) and the metric's
+    own read of both (+ the climatology for ACC)."""
+    PEAK = 8.0e12
+    H, W, C, B = 721, 1440, 73, 1
+    N = H * W
+    names = ["u10m", "t2m", "sp", "sst", "u500", "z500", "q500", "q50"] + [f"x{i}" for i in range(C - 8)]
+
+    class P(dict):
+        __getattr__ = dict.__getitem__
+
+    rate = lambda nbytes, ms: f"{nbytes / (ms * 1e-3) / 1e12:5.2f} TB/s = {nbytes / (ms * 1e-3) / PEAK * 100:5.1f} % of the HBM roof"
+    with torch.no_grad():
+        clim = torch.randn(1, C, H, W)
+        for E, dt in ((16, torch.bfloat16), (1, torch.float32)):
+            s = 2 if dt == torch.bfloat16 else 4
+            params = P(channel_names=names, dt=1, dhours=6, img_shape_x_resampled=H, img_shape_y_resampled=W, ensemble_size=E)
+            kw = {} if E > 1 else dict(crps_var_names=[], spread_var_names=[], ssr_var_names=[])
+            h = ma.MetricsHandler(params, clim, 4, dev, **kw)
+            h.initialize_buffers()
+            h.zero_buffers()
+            prd = torch.randn((B, E, C, H, W) if E > 1 else (B, C, H, W), device=dev).to(dt)
+            tar = (prd.float().mean(dim=1) if E > 1 else prd.float()) + torch.randn(B, C, H, W, device=dev)
+            tar = tar.to(dt)
+            loss = torch.zeros((), device=dev)
+            J, nh = 8, len(h.metric_handles)
+            ndet, nens = 3, nh - 3
+            fused_bytes = ((E + 1) * J * s + 4 + J * 4) * N
+            comp_bytes = ((E * C * s + C * 4) if E > 1 else 0) * N
+            comp_bytes += ndet * (2 * J * 4 + 2 * J * s + J * s + J * 4 + J * s) * N + J * 4 * N          # + ACC's climatology
+            comp_bytes += nens * (2 * E * J * s + 2 * J * s + J * s + (E + 1) * J * s) * N
+
+            def run(fused):
+                h.use_fused = fused
+                h.update(prd, tar, loss, 1)
+
+            for rnd in range(3):
+                tf, tc = timeit(lambda: run(True), reps=20, warm=3), timeit(lambda: run(False), reps=5, warm=2)
+                print(f"mhandler E={E:2d} {str(dt)[6:]} {nh} handles round {rnd}: fused {tf:7.3f} ms {rate(fused_bytes, tf)} ({fused_bytes / 1e9:.2f} GB)"
+                      f" | composed {tc:8.3f} ms {rate(comp_bytes, tc)} ({comp_bytes / 1e9:.2f} GB) = {tc / tf:5.1f} x", flush=True)
+            del prd, tar, h
 
 
 if __name__ == "__main__":
