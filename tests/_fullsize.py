@@ -13,6 +13,8 @@ import time
 
 import torch
 
+from _ranks import share_gpu  # noqa: F401  (tools/dist_diag.py imports it from here)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CACHE_DIR = os.environ.get("MAKANI_AMD_TEST_CACHE", os.path.join(tempfile.gettempdir(), "makani_amd_test_cache"))
 
@@ -20,20 +22,6 @@ CACHE_DIR = os.environ.get("MAKANI_AMD_TEST_CACHE", os.path.join(tempfile.gettem
 CONFIG2 = dict(inp_shape=(721, 1440), out_shape=(721, 1440), inp_chans=73, out_chans=73, scale_factor=3, embed_dim=384,
                num_layers=8, mlp_ratio=2, operator_type="dhconv", normalization_layer="instance_norm",
                activation_function="gelu", big_skip=True, model_grid_type="equiangular", sht_grid_type="legendre-gauss")
-
-
-def share_gpu(rank, world, ncu=256):
-    """Round 5 gave the ranks that share ONE GPU in a test disjoint compute units (``HSA_CU_MASK``) because kernels of different
-    processes on one compute unit disturbed each other's results.  Round 6 found the cause — packed-fp32 instructions that read a
-    VGPR src1 through op_sel are unreliable on gfx950 while certain matrix-core kernels share the compute unit
-    (docs/LAB_NOTEBOOK.md 6.1, tools/pk_hazard_probe.py) — and removed those instruction forms from every kernel
-    (tools/pk_opsel_scan.py, tests/test_packed_forms.py).  The tests therefore run WITHOUT the mask: N ranks on one GPU share
-    all compute units, which is the stronger check.  ``MAKANI_AMD_TEST_CU_MASK=1`` brings the mask back (must be in the
-    environment before the process's first GPU call)."""
-    if os.environ.get("MAKANI_AMD_TEST_CU_MASK", "0") != "1":
-        return
-    per = max(1, ncu // max(1, world))
-    os.environ["HSA_CU_MASK"] = f"0:{rank * per}-{(rank + 1) * per - 1}"
 
 
 def host_threads(cap=64):
@@ -127,22 +115,6 @@ def config2_oracle():
     reference's own CPU bf16 autocast), ONE backward pass of sum(y * g) in fp32 and one under bf16 autocast — input gradient
     and the gradient of every parameter (about three minutes on the GPU box's host the first time, then a file)"""
     return cached(f"config2_oracle_{_oracle_fingerprint()}.pt", _compute_config2_oracle)
-
-
-def spawn(fn, args, nprocs, timeout_s):
-    """``mp.spawn`` with a deadline: a schedule bug between ranks is a hang, and a hung GPU box is worse than a red test"""
-    import torch.multiprocessing as mp
-    ctx = mp.spawn(fn, args=args, nprocs=nprocs, join=False)
-    deadline = time.time() + timeout_s
-    while True:
-        left = deadline - time.time()
-        if left <= 0:
-            for p in ctx.processes:
-                if p.is_alive():
-                    p.kill()
-            raise TimeoutError(f"{fn.__name__}: {nprocs} ranks did not finish within {timeout_s} s")
-        if ctx.join(timeout=min(left, 5.0)):
-            return
 
 
 def log_line(text):

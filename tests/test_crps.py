@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+from _ranks import launch, ranks
 from conftest import load_golden, rel_l2
 
 
@@ -170,17 +171,11 @@ def test_spectral_crps_matches_reference_golden():
             assert c["crps_type"] == "gauss"
 
 
-def _worker_ensemble(rank, world, port):
+def _worker_ensemble(rank, world, rendezvous):
     """ensemble_distributed=True (crps_loss.py:305-307,362-373,441-442,566-581): 2 batch entries x 2 ensemble ranks on one GPU,
     three members per rank: value and forecast gradient of CRPSLoss (every score type) and SpectralCRPSLoss against the
     serial modules on the gathered ensemble"""
-    import os, sys
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -210,16 +205,8 @@ def _worker_ensemble(rank, world, port):
             (out * g).sum().backward()
             assert rel_l2(out, ref) < 1e-5, (cls.__name__, ctype, out, ref)
             assert rel_l2(fl.grad, fs.grad[:, ie * El:(ie + 1) * El]) < 2e-5, (cls.__name__, ctype)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.gpu
 def test_ensemble_parallel_crps_matches_serial():
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mp.spawn(_worker_ensemble, args=(4, port), nprocs=4, join=True)
+    launch(_worker_ensemble, 4, limit=240)

@@ -7,31 +7,11 @@
    makani_amd.distributed (data-parallel mean, per-group sums from the is_shared_mp annotations)."""
 import math
 import os
-import socket
-import sys
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-
-def _teardown():
-    """every rank waits for the others before it tears its process group down: a rank that leaves while a peer is still inside
-    a gloo collective makes the peer's transport thread throw ("terminate called without an active exception", seen once in
-    five runs of the 4-rank ZeRO test: VERDICT r5 weak #11)"""
-    try:
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+from _ranks import hw_groups, launch, ranks
 
 
 class OracleBackend:
@@ -154,23 +134,11 @@ def _complex_to_s(c):
     return torch.nn.functional.pad(S, (0, (-C) % 4)).reshape(L, M, 2, -1).contiguous()
 
 
-def _worker_sht(rank, world, port, h, w, nlat, nlon, lmax, mmax, grid, B, C, fused=False, chunks="2"):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_sht(rank, world, rendezvous, h, w, nlat, nlon, lmax, mmax, grid, B, C, fused=False, chunks="2"):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.distributed as thd
         from oracle import sht as osht
-        ih, iw = rank // w, rank % w
-        hg = wg = None
-        for j in range(w):                       # polar groups: same iw
-            g = dist.new_group([i * w + j for i in range(h)])
-            if j == iw:
-                hg = g
-        for i in range(h):                       # azimuth groups: same ih
-            g = dist.new_group([i * w + j for j in range(w)])
-            if i == ih:
-                wg = g
+        ih, iw, hg, wg = hw_groups(rank, h, w)           # polar group: same iw; azimuth group: same ih
         thd.init(hg if h > 1 else None, wg if w > 1 else None, dist.group.WORLD)
         thd._BACKEND = OracleSegBackend if fused else OracleBackend      # test-only: the CPU stand-in for the HIP kernels
         os.environ["MAKANI_AMD_DIST_CHUNKS"] = chunks
@@ -223,17 +191,13 @@ def _worker_sht(rank, world, port, h, w, nlat, nlon, lmax, mmax, grid, B, C, fus
         tri = torch.tril(torch.ones(lmax, mmax, dtype=torch.bool))[l0:l0 + ll, m0:m0 + ml]
         gc_ref = cs.grad[..., l0:l0 + ll, m0:m0 + ml]
         assert ((cl.grad - gc_ref) * tri).abs().max().item() < 1e-5 * max(1.0, gc_ref.abs().max().item())
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2)])
 @pytest.mark.parametrize("nlat,nlon,lmax,mmax,grid,B,C", [(33, 64, 16, 17, "equiangular", 1, 6), (12, 24, 12, 13, "legendre-gauss", 2, 8),
                                                     (12, 24, 12, 13, "legendre-gauss", 2, 3)])
 def test_distributed_sht_schedule_matches_serial(h, w, nlat, nlon, lmax, mmax, grid, B, C):
-    world = h * w
-    mp.spawn(_worker_sht, args=(world, _free_port(), h, w, nlat, nlon, lmax, mmax, grid, B, C), nprocs=world, join=True)
+    launch(_worker_sht, h * w, h, w, nlat, nlon, lmax, mmax, grid, B, C, limit=240)
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2), (4, 2), (3, 1)])
@@ -243,24 +207,20 @@ def test_fused_distributed_sht_schedule_matches_serial(h, w, nlat, nlon, lmax, m
     """the fused schedule of makani_amd/dist_pipeline.py (per-peer slabs written / read by the FFT, ONE h x w all-to-all between
     FFT and Legendre transform, latitude-major Legendre operand, plane blocks): forward and backward of both transforms against
     the serial oracle, incl. ragged plane blocks (fewer planes than ranks, padded sub-blocks) and empty slabs"""
-    world = h * w
-    mp.spawn(_worker_sht, args=(world, _free_port(), h, w, nlat, nlon, lmax, mmax, grid, B, C, True), nprocs=world, join=True)
+    launch(_worker_sht, h * w, h, w, nlat, nlon, lmax, mmax, grid, B, C, True, limit=240)
 
 
 def test_fused_distributed_sht_latitude_chunks():
     """steps (2)+(3) cut into latitude chunks (MAKANI_AMD_DIST_CHUNKS): every rank enters the same number of collectives even
     when the ranks' latitude counts differ (ragged 130 -> [44, 43, 43]...)"""
-    mp.spawn(_worker_sht, args=(4, _free_port(), 2, 2, 130, 48, 20, 21, "equiangular", 1, 5, True, "2"), nprocs=4, join=True)
+    launch(_worker_sht, 4, 2, 2, 130, 48, 20, 21, "equiangular", 1, 5, True, "2", limit=240)
 
 
-def _worker_disagree(rank, world, port, what):
+def _worker_disagree(rank, world, rendezvous, what):
     """ranks whose environment differs must agree on the schedule before the first collective of a transform: a differing
     chunk count raises on EVERY rank (instead of a hang in mismatched collectives), a differing MAKANI_AMD_DIST_FUSED makes
     every rank run the transpose-by-transpose schedule"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.distributed as thd
         from makani_amd import dist_pipeline as dp
         wg = dist.new_group([0, 1])
@@ -280,21 +240,15 @@ def _worker_disagree(rank, world, port, what):
             assert dp.eligible(fwd, x.dtype) is False          # rank 0 alone would have taken the fused schedule
             S = fwd.analysis(x)                                  # ... and both ranks complete the same (plain) schedule
             assert S.shape[0] == lmax
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("what", ["chunks", "fused"])
 def test_ranks_agree_on_the_exchange_schedule(what):
-    mp.spawn(_worker_disagree, args=(2, _free_port(), what), nprocs=2, join=True)
+    launch(_worker_disagree, 2, what, limit=240)
 
 
-def _worker_dp(rank, world, port):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_dp(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         mcomm.init(1, 1)
@@ -316,21 +270,16 @@ def _worker_dp(rank, world, port):
             assert torch.allclose(torch.view_as_real(model.c.grad), torch.full((4, 2, 2), mean + 1.0))
             assert torch.allclose(model.big.grad, torch.full_like(model.big, (world - 1) / 2))
             assert not net.reducer.pending and not net.reducer.small
-    finally:
-        _teardown()
 
 
 def test_data_parallel_grad_reducer_world2():
-    mp.spawn(_worker_dp, args=(2, _free_port()), nprocs=2, join=True)
+    launch(_worker_dp, 2, limit=240)
 
 
-def _worker_no_sync(rank, world, port):
+def _worker_no_sync(rank, world, rendezvous):
     """gradient accumulation over two micro-batches with ``no_sync()`` around the first (deterministic_trainer.py:531-546)
     against the reduction of the summed gradients: identical results, and NO collective inside the context"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         mcomm.init(1, 1)
@@ -370,23 +319,18 @@ def _worker_no_sync(rank, world, port):
         except KeyError:
             pass
         assert net.reducer.enabled
-    finally:
-        _teardown()
 
 
 def test_grad_reduce_wrapper_no_sync_gradient_accumulation_world2():
-    mp.spawn(_worker_no_sync, args=(2, _free_port()), nprocs=2, join=True)
+    launch(_worker_no_sync, 2, limit=240)
 
 
-def _worker_tree(rank, world, port, ph, pw):
+def _worker_tree(rank, world, rendezvous, ph, pw):
     """makani_amd.comm.init (makani/utils/comm.py:114-201) + the gradient reductions of makani/mpu/mappings.py:460-523
     driven by the is_shared_mp annotations: dhconv weights (["matmul", "w"], l-sharded over h) are summed over "w" only,
     ["spatial"] / un-annotated parameters over the whole model instance, a position embedding ([]) over nothing; then
     the data-parallel mean.  Also the sharded gradient norm (training_helpers.py:123-160)."""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         msize = ph * pw
@@ -431,24 +375,18 @@ def _worker_tree(rank, world, port, ph, pw):
         sq_w = sum(72 * over_data(lambda d, i=i: r1([d * msize + i * pw + j for j in range(pw)])) ** 2 for i in range(ph))
         exp_norm = math.sqrt(sq_w + 6 * exp_sp ** 2 + 2 * exp_sp ** 2 + 3 * exp_pos ** 2)
         assert abs(float(thd.total_grad_norm(model)) - exp_norm) < 1e-3 * exp_norm
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("world,ph,pw", [(2, 1, 1), (4, 2, 1), (4, 1, 2), (4, 2, 2), (8, 2, 2)])
 def test_group_tree_and_model_parallel_grad_reduction(world, ph, pw):
-    mp.spawn(_worker_tree, args=(world, _free_port(), ph, pw), nprocs=world, join=True)
+    launch(_worker_tree, world, ph, pw, limit=240)
 
 
-def _worker_ragged(rank, world, port, h, w, C, fused=False):
+def _worker_ragged(rank, world, rendezvous, h, w, C, fused=False):
     """BASELINE configs[2] / [4] split sizes at the real grid: 721 x 1440, lmax 240, mmax 241 over h = 4 (lat
     [181, 181, 181, 178], l [60] * 4) and w = 2 (lon [720, 720], m [121, 120]), reduced channel count"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         from oracle import sht as osht
@@ -483,9 +421,6 @@ def _worker_ragged(rank, world, port, h, w, C, fused=False):
         yref = osht.InverseRealSHT(nlat, nlon, lmax=lmax, mmax=mmax, grid="equiangular")(coef)
         assert y.shape == (B, C, hl, wl)
         assert (y - yref[..., lat0:lat0 + hl, lon0:lon0 + wl]).abs().max().item() < 1e-6 * yref.abs().max().item()
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("h,w,C", [(4, 1, 6), (4, 2, 5)])
@@ -493,7 +428,7 @@ def _worker_ragged(rank, world, port, h, w, C, fused=False):
 def test_distributed_sht_ragged_config3_splits(h, w, C, fused):
     """h = 4 (BASELINE configs[2]) and h4 w2 (configs[4]) at 721 x 1440 with ragged plane counts (6 planes over 4 ranks ->
     [1, 1, 1, 3]; 5 over 2 -> [3, 2]); transpose-by-transpose and fused schedule"""
-    mp.spawn(_worker_ragged, args=(h * w, _free_port(), h, w, C, fused), nprocs=h * w, join=True)
+    launch(_worker_ragged, h * w, h, w, C, fused, limit=240)
 
 
 def test_parse_parallelism():
@@ -508,11 +443,8 @@ def test_parse_parallelism():
 # --------------------------------------------------------------------------- #
 # ZeRO-1: reduce-scattered gradients + sharded optimizer state + in-place parameter all-gather
 # --------------------------------------------------------------------------- #
-def _worker_zero(rank, world, port):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_zero(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         import makani_amd.optim as mo
@@ -593,13 +525,11 @@ def _worker_zero(rank, world, port):
         opt2 = mo.FusedAdamW(model.parameters(), lr=1e-2, betas=(0.9, 0.95), eps=1e-8, weight_decay=0.1)
         opt2.load_state_dict(fsd)
         assert opt2.state[model.w]["exp_avg"].numel() == 3072 and "zero_shard" not in opt2.state[model.w]
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_zero1_sharded_adamw_matches_single_process_adamw(world):
-    mp.spawn(_worker_zero, args=(world, _free_port()), nprocs=world, join=True)
+    launch(_worker_zero, world, limit=240)
 
 
 # --------------------------------------------------------------------------- #
@@ -625,23 +555,11 @@ def _psi_contract(x, psi, nlat_out, nlon_out, window=None):
     return y.reshape(B, C * K, nlat_out, nlon_out)
 
 
-def _worker_disco(rank, world, port, h, w):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_disco(rank, world, rendezvous, h, w):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd.distributed as thd
         from makani_amd import disco
-        ih, iw = rank // w, rank % w
-        hg = wg = None
-        for j in range(w):
-            g = dist.new_group([i * w + j for i in range(h)])
-            if j == iw:
-                hg = g
-        for i in range(h):
-            g = dist.new_group([i * w + j for j in range(w)])
-            if i == ih:
-                wg = g
+        ih, iw, hg, wg = hw_groups(rank, h, w)
         thd.init(hg if h > 1 else None, wg if w > 1 else None)
         for in_shape, out_shape, C, kshape, basis in (((19, 36), (10, 18), 5, (3, 3), "morlet"), ((13, 24), (13, 24), 4, (3, 3), "morlet"),
                                                       ((13, 24), (7, 12), 1, (3, 3), "morlet"), ((13, 24), (13, 24), 2, (3, 4), "piecewise linear"),
@@ -673,11 +591,8 @@ def _worker_disco(rank, world, port, h, w):
             if hg is not None and h > 1:
                 dist.all_reduce(cnt, group=hg)
             assert int(cnt) == d._psi["v"].size
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2), (3, 1)])
 def test_distributed_disco_schedule_matches_serial(h, w):
-    mp.spawn(_worker_disco, args=(h * w, _free_port(), h, w), nprocs=h * w, join=True)
+    launch(_worker_disco, h * w, h, w, limit=240)

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import _escore_ref as ref
+from _ranks import launch, ranks
 from conftest import load_golden, rel_l2
 
 KW = dict(img_shape=(9, 16), crop_shape=(9, 16), crop_offset=(0, 0), channel_names=["u500", "v500", "t2m"], grid_type="equiangular")
@@ -151,17 +152,11 @@ def test_escore_bf16_forecasts(p):
     assert rel_l2(gb.float(), gf) < 2.0 ** -9
 
 
-def _worker_ensemble(rank, world, port):
+def _worker_ensemble(rank, world, rendezvous):
     """ensemble_distributed=True (energy_score.py:139-151,188-190,373-386,416-418,559-571,600-602): 2 batch entries x 2 ensemble
     ranks on one GPU, three members per rank: value and local-member gradient of the three classes against the serial modules
     on the gathered ensemble"""
-    import os, sys
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -191,16 +186,8 @@ def _worker_ensemble(rank, world, port):
             (out * g).sum().backward()
             assert rel_l2(out, ref_out) < 1e-5, (cls.__name__, out, ref_out)
             assert rel_l2(fl.grad, fs.grad[:, ie * El:(ie + 1) * El]) < 2e-5, cls.__name__
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.gpu
 def test_ensemble_parallel_escore_matches_serial():
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mp.spawn(_worker_ensemble, args=(4, port), nprocs=4, join=True)
+    launch(_worker_ensemble, 4, limit=240)

@@ -18,8 +18,8 @@ import pytest
 import torch
 
 import _coherence_ref as ref
+from _ranks import launch, ranks
 from conftest import load_golden, rel_l2
-from test_gpu_restloss import _setup, _spawn
 
 TOL = 1e-5
 OFF = 1 << 30
@@ -306,11 +306,10 @@ PARALLEL_FORMS = [("SpectralCoherenceLoss", dict(channel_reduction=False)), ("Sp
                   ("SpectralRegularization", dict()), ("SpectralRegularization", dict(logarithmic=True))]
 
 
-def _worker_ensemble(rank, world, port):
+def _worker_ensemble(rank, world, rendezvous):
     """two ensemble ranks, two members each: ensemble_distributed=True against the serial modules on the gathered ensemble
     (value) and its local members (gradient)"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -335,16 +334,12 @@ def _worker_ensemble(rank, world, port):
             errs = rel_l2(out, want), rel_l2(fl.grad, fs.grad[:, ie * El:(ie + 1) * El])
             print(f"rank {rank} {cls} {extra}: value {errs[0]:.2e} gradient {errs[1]:.2e}", flush=True)
             assert max(errs) < TOL, (cls, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_spatial(rank, world, port):
+def _worker_spatial(rank, world, rendezvous):
     """h2 x w2 on a 37 x 72 grid (19 + 18 latitudes; the w rank 1 holds no order 0): spatial_distributed=True against the
     serial modules: value, and the local shard of the forecast gradient"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -371,16 +366,13 @@ def _worker_spatial(rank, world, port):
             errs = rel_l2(out, want), rel_l2(fl.grad, fs.grad[..., hs, ws])
             print(f"rank {rank} (h {ih}, w {iw}) {cls} {extra}: value {errs[0]:.2e} gradient {errs[1]:.2e}", flush=True)
             assert max(errs) < TOL, (cls, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.gpu
 def test_ensemble_parallel_losses_match_serial():
-    _spawn(_worker_ensemble, 2)
+    launch(_worker_ensemble, 2, limit=240)
 
 
 @pytest.mark.gpu
 def test_spatially_parallel_losses_match_serial():
-    _spawn(_worker_spatial, 4)
+    launch(_worker_spatial, 4, limit=240)

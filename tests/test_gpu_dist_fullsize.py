@@ -13,26 +13,17 @@ makani/mpu/mappings.py:321-525, makani/models/stepper.py:224-284.  Tolerances: f
 (tests/distributed/tests_distributed_layers.py:71-76); bf16 relative to the reference's own CPU bf16 arithmetic on the
 same shard (tests/test_gpu_headline.py explains why the flat 2e-2 cannot hold through eight bf16 layers)."""
 import os
-import socket
-import sys
 import time
 
 import pytest
 import torch
-import torch.distributed as dist
 
-from _fullsize import CACHE_DIR, CONFIG2, config2_oracle, log_line, spawn
+from _fullsize import CACHE_DIR, CONFIG2, config2_oracle, log_line
+from _ranks import launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-4
 BIG = ("filter.filter.weight", "fwd.0.weight", "fwd.2.weight", "fwd.3.weight", "outer_skip.weight")
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _r(t):
@@ -42,10 +33,10 @@ def _r(t):
     return t
 
 
-def _rel(a, b):
-    a, b = _r(a).cpu().double(), _r(b).cpu().double()
+def _rel_real(a, b):
+    a, b = _r(a).cpu(), _r(b).cpu()
     assert a.shape == b.shape, (a.shape, b.shape)
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+    return rel(a, b)
 
 
 def _absmax(a, b):
@@ -74,7 +65,7 @@ def serial_hip(oracle):
     out = dict(y=y.detach().cpu(), gx=xd.grad.cpu(),
                grads={n: (torch.view_as_real(p.grad).cpu().contiguous() if p.grad.is_complex() else p.grad.cpu().contiguous())
                       for n, p in model.named_parameters()})
-    e = _rel(out["y"], oracle["y"])
+    e = _rel_real(out["y"], oracle["y"])
     assert e < TOL, e
     os.makedirs(CACHE_DIR, exist_ok=True)
     torch.save(out, path)
@@ -85,19 +76,6 @@ def serial_hip(oracle):
         os.remove(path)
     except OSError:
         pass
-
-
-def _setup_rank(rank, world, port, h, w):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    torch.set_num_threads(8)
-    from _fullsize import share_gpu
-    share_gpu(rank, world)                  # disjoint compute units per rank, set before the first GPU call (tests/_fullsize.py)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    import makani_amd.comm as mcomm
-    return mcomm.init(h, w)
 
 
 def _contract(state, scale):
@@ -152,10 +130,12 @@ def _assert_fused_two_chunks(model, h, w):
         assert model.trans_down.lon_shapes == [720, 720] and model.trans_down.m_shapes == [121, 120]
 
 
-def _worker_fwd_bwd(rank, world, port, h, w, amp, hip_path):
-    _, ih, iw = _setup_rank(rank, world, port, h, w)
-    try:
+def _worker_fwd_bwd(rank, world, rendezvous, h, w, amp, hip_path):
+    torch.set_num_threads(8)
+    with ranks(rank, world, rendezvous):
+        import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
+        _, ih, iw = mcomm.init(h, w)
         from _fullsize import config2_oracle, log_line
         dev = torch.device("cuda:0")
         oracle = config2_oracle()
@@ -181,11 +161,11 @@ def _worker_fwd_bwd(rank, world, port, h, w, amp, hip_path):
 
         errs = {}
         if not amp:
-            errs["y"] = (_rel(yl, oracle["y"][sl]), _rel(yl, hip["y"][sl]))
-            errs["gx"] = (_rel(xl.grad, oracle["gx"][sl]), _rel(xl.grad, hip["gx"][sl]))
+            errs["y"] = (_rel_real(yl, oracle["y"][sl]), _rel_real(yl, hip["y"][sl]))
+            errs["gx"] = (_rel_real(xl.grad, oracle["gx"][sl]), _rel_real(xl.grad, hip["gx"][sl]))
         else:
-            errs["y"] = (_rel(yl.float(), oracle["y"][sl]), _rel(oracle["y_bf16"][sl], oracle["y"][sl]))
-            errs["gx"] = (_rel(xl.grad, oracle["gx"][sl]), _rel(oracle["bf16_gx"][sl], oracle["gx"][sl]))
+            errs["y"] = (_rel_real(yl.float(), oracle["y"][sl]), _rel_real(oracle["y_bf16"][sl], oracle["y"][sl]))
+            errs["gx"] = (_rel_real(xl.grad, oracle["gx"][sl]), _rel_real(oracle["bf16_gx"][sl], oracle["gx"][sl]))
         gmax = max(float(_r(v).abs().max()) for v in oracle["grads"].values())
         worst, bad = ("", 0.0), {}
         for n, p in model.named_parameters():
@@ -195,7 +175,7 @@ def _worker_fwd_bwd(rank, world, port, h, w, amp, hip_path):
             if not amp:
                 hg = hip["grads"][n]
                 hg = hg[..., l0:l0 + ll, :] if spectral else hg                  # (the HIP file holds real views)
-                e, e2, a = _rel(p.grad, ref), _rel(_r(p.grad), hg), _absmax(p.grad, ref)
+                e, e2, a = _rel_real(p.grad, ref), _rel_real(_r(p.grad), hg), _absmax(p.grad, ref)
                 errs[n] = (e, e2)
                 # gradients that are exactly zero by construction (a per-channel constant in front of an instance norm) are
                 # accepted on the absolute scale of the largest gradient entry, as in tests/test_gpu_headline.py
@@ -204,7 +184,7 @@ def _worker_fwd_bwd(rank, world, port, h, w, amp, hip_path):
                 if e > worst[1] and a >= 1e-5 * gmax:
                     worst = (n, e)
             elif n.endswith(BIG):
-                e, e_ref = _rel(p.grad, ref), _rel(pick(oracle["bf16_grads"][n]), ref)
+                e, e_ref = _rel_real(p.grad, ref), _rel_real(pick(oracle["bf16_grads"][n]), ref)
                 errs[n] = (e, e_ref)
                 if not (e < 0.15 and e <= 1.25 * e_ref):
                     bad[n] = (e, e_ref)
@@ -227,9 +207,6 @@ def _worker_fwd_bwd(rank, world, port, h, w, amp, hip_path):
             assert errs["y"][0] < 6e-2 * 1.5 and errs["y"][0] <= 1.25 * errs["y"][1], (rank, errs["y"])
             assert errs["gx"][0] < 0.15 and errs["gx"][0] <= 1.25 * errs["gx"][1], (rank, errs["gx"])
         assert not bad, (rank, bad)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,amp", [(4, 1, False), (4, 2, False), (4, 2, True)])
@@ -237,7 +214,7 @@ def test_config2_fullsize_spatial_parallel_fwd_bwd(h, w, amp, oracle, serial_hip
     """BASELINE configs[2] (h = 4) and the model instance of configs[4] (h4 w2): whole network, full size, forward + backward
     with the gradient hooks; fused schedule with two latitude chunks asserted; per-rank peak memory logged"""
     log_line(f"--- test_config2_fullsize_spatial_parallel_fwd_bwd h{h} w{w} {'bf16 autocast' if amp else 'fp32'} ---")
-    spawn(_worker_fwd_bwd, (h * w, _free_port(), h, w, amp, serial_hip), h * w, timeout_s=900)
+    launch(_worker_fwd_bwd, h * w, h, w, amp, serial_hip, limit=900)
 
 
 # --------------------------------------------------------------------------- #
@@ -272,16 +249,16 @@ def serial_rollout(oracle):
     G = torch.randn(1, 73 * (NF + 1), 721, 1440, generator=torch.Generator().manual_seed(5))
     plain = _serial_rollout_pass(model, net, oracle, G, False)
     chaos = _serial_rollout_pass(model, net, oracle, G, True)
-    log_line(f"--- serial HIP 4-step rollout at 721x1440, the oracle's weights: bf16 autocast vs fp32: y {_rel(chaos['y'], plain['y']):.2e}  "
-             f"gx {_rel(chaos['gx'], plain['gx']):.2e} (chaotic: not a gate) ---")
+    log_line(f"--- serial HIP 4-step rollout at 721x1440, the oracle's weights: bf16 autocast vs fp32: y {_rel_real(chaos['y'], plain['y']):.2e}  "
+             f"gx {_rel_real(chaos['gx'], plain['gx']):.2e} (chaotic: not a gate) ---")
     del chaos
     scale, f32, yard = None, None, None
     for sc in (0.02, 0.01):          # (0.2 / 0.1 / 0.05 were measured: y 9.0e-2 / 3.7e-2 / 1.2e-2, gx 0.64 / 0.42 / 0.18: docs/LAB_NOTEBOOK.md 6.6)
         model.load_state_dict(_contract(oracle["state"], sc), strict=True)
         f32 = _serial_rollout_pass(model, net, oracle, G, False)
         b16 = _serial_rollout_pass(model, net, oracle, G, True)
-        yard = dict(y=_rel(b16["y"], f32["y"]), gx=_rel(b16["gx"], f32["gx"]),
-                    grads={n: _rel(b16["grads"][n], f32["grads"][n]) for n in f32["grads"]})
+        yard = dict(y=_rel_real(b16["y"], f32["y"]), gx=_rel_real(b16["gx"], f32["gx"]),
+                    grads={n: _rel_real(b16["grads"][n], f32["grads"][n]) for n in f32["grads"]})
         log_line(f"--- serial HIP 4-step rollout, contractive weights (scale {sc}): bf16 autocast vs fp32: y {yard['y']:.2e}  gx {yard['gx']:.2e}  "
                  f"weight gradients {min(yard['grads'].values()):.2e}..{max(yard['grads'].values()):.2e}  "
                  f"peak {torch.cuda.max_memory_allocated() / 2 ** 30:.1f} GiB ---")
@@ -304,10 +281,12 @@ def serial_rollout(oracle):
         pass
 
 
-def _worker_rollout(rank, world, port, h, w, amp, ref_path):
-    _, ih, iw = _setup_rank(rank, world, port, h, w)
-    try:
+def _worker_rollout(rank, world, rendezvous, h, w, amp, ref_path):
+    torch.set_num_threads(8)
+    with ranks(rank, world, rendezvous):
+        import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
+        _, ih, iw = mcomm.init(h, w)
         from makani_amd.stepper import MultiStepWrapper
         from _fullsize import config2_oracle, log_line
         dev = torch.device("cuda:0")
@@ -332,7 +311,7 @@ def _worker_rollout(rank, world, port, h, w, amp, ref_path):
         torch.cuda.synchronize()
         t2 = time.time()
         _assert_fused_two_chunks(model, h, w)
-        e_y, e_gx = _rel(yl.float(), ry[sl]), _rel(xl.grad, rgx[sl])
+        e_y, e_gx = _rel_real(yl.float(), ry[sl]), _rel_real(xl.grad, rgx[sl])
         y_y, y_gx = float(ref["yard_y"]), float(ref["yard_gx"])
         worst, bad = ("", 0.0), {}
         for n, p in model.named_parameters():
@@ -340,7 +319,7 @@ def _worker_rollout(rank, world, port, h, w, amp, ref_path):
                 continue
             r = rgrads[n]
             r = r[..., l0:l0 + ll, :] if n.endswith("filter.filter.weight") else r
-            e, yd = _rel(_r(p.grad), r), float(ref["yard_grads"][n])
+            e, yd = _rel_real(_r(p.grad), r), float(ref["yard_grads"][n])
             tol = 1.25 * yd if amp else TOL_ROLLOUT
             if e > tol:
                 bad[n] = (e, tol)
@@ -361,9 +340,6 @@ def _worker_rollout(rank, world, port, h, w, amp, ref_path):
         else:
             assert e_y < TOL_ROLLOUT and e_gx < TOL_ROLLOUT, (rank, e_y, e_gx)
         assert not bad, (rank, bad)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 TOL_ROLLOUT = 1e-3      # four chained steps: the fp32 differences of one step (3e-6 / 6e-6) grow with every re-entry
@@ -377,4 +353,4 @@ def test_config5_fullsize_multistep4_h4w2_checkpointed(amp, oracle, serial_rollo
     configuration's precision) on CONTRACTIVE weights, where the serial bf16 rollout stays within 0.1 of its fp32 rollout and the
     distributed one must stay within 1.25 x that distance — a gate a wrong shard fails"""
     log_line(f"--- test_config5_fullsize_multistep4_h4w2_checkpointed {'bf16 autocast' if amp else 'fp32'} ---")
-    spawn(_worker_rollout, (8, _free_port(), 4, 2, amp, serial_rollout), 8, timeout_s=1200)
+    launch(_worker_rollout, 8, 4, 2, amp, serial_rollout, limit=1200)

@@ -4,27 +4,15 @@ Legendre kernels, l-sharded dhconv weights with triangular shard offsets, distri
 runs end to end and is compared with the serial HIP model (the pattern of the reference's
 tests/distributed/tests_distributed_layers.py:69-223 and tests_distributed_model.py:218-330)."""
 import os
-import socket
 import sys
 
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import hw_groups, join_group, launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
-
 
 # distributed against serial HIP in fp32, 16-channel toy network.  Rounds 2-4 needed 1e-4 / 2e-4 / 5e-4 here because the ranks
 # shared compute units (docs/LAB_NOTEBOOK.md 5.1); with a compute-unit range per rank the two schedules agree to summation order:
@@ -32,15 +20,8 @@ def _rel(a, b):
 TOL_Y, TOL_G = 5e-6, 2e-5
 
 
-def _worker(rank, world, port, h, w, norm="instance_norm", operator_type="dhconv", separable=False, max_modes=None):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # ranks sharing ONE GPU get disjoint compute units, set before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker(rank, world, rendezvous, h, w, norm="instance_norm", operator_type="dhconv", separable=False, max_modes=None):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd as ma
         import makani_amd.distributed as thd
         dev = torch.device("cuda:0")
@@ -57,16 +38,7 @@ def _worker(rank, world, port, h, w, norm="instance_norm", operator_type="dhconv
         ys = serial(xs)
         (ys * G).sum().backward()
 
-        ih, iw = rank // w, rank % w
-        hg = wg = None
-        for j in range(w):
-            g = dist.new_group([i * w + j for i in range(h)])
-            if j == iw:
-                hg = g
-        for i in range(h):
-            g = dist.new_group([i * w + j for j in range(w)])
-            if i == ih:
-                wg = g
+        ih, iw, hg, wg = hw_groups(rank, h, w)
         thd.init(hg if h > 1 else None, wg if w > 1 else None, dist.group.WORLD)
         model = ma.SphericalFourierNeuralOperatorNet(**cfg).to(dev)
         assert model.spatial_parallel
@@ -93,8 +65,8 @@ def _worker(rank, world, port, h, w, norm="instance_norm", operator_type="dhconv
         yl = model(xl)
         (yl * G[..., lat0:lat0 + hl, lon0:lon0 + wl]).sum().backward()
         assert yl.shape == (B, 4, hl, wl)
-        e_y = _rel(yl, ys[..., lat0:lat0 + hl, lon0:lon0 + wl])
-        e_gx = _rel(xl.grad, xs.grad[..., lat0:lat0 + hl, lon0:lon0 + wl])
+        e_y = rel(yl, ys[..., lat0:lat0 + hl, lon0:lon0 + wl])
+        e_gx = rel(xl.grad, xs.grad[..., lat0:lat0 + hl, lon0:lon0 + wl])
         assert e_y < TOL_Y and e_gx < TOL_G, (rank, e_y, e_gx)
         sref = dict(serial.named_parameters())
         worst = ("", 0.0)
@@ -109,19 +81,15 @@ def _worker(rank, world, port, h, w, norm="instance_norm", operator_type="dhconv
                 ref = sref[k].grad.cpu()
             if k.endswith("mlp.fwd.3.bias"):                 # (exactly zero by construction: a constant in front of an instance norm)
                 continue
-            e = _rel(g, ref)
+            e = rel(g, ref)
             worst = max(worst, (k, e), key=lambda t: t[1])
             assert e < TOL_G, (rank, k, e)
         print(f"h{h}w{w} {norm} {operator_type}{' separable' if separable else ''} rank {rank}: y {e_y:.1e} gx {e_gx:.1e} worst parameter gradient {worst[0]} {worst[1]:.1e}", flush=True)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2)])
 def test_spatial_parallel_sfno_matches_serial(h, w):
-    world = h * w
-    mp.spawn(_worker, args=(world, _free_port(), h, w), nprocs=world, join=True)
+    launch(_worker, h * w, h, w, limit=240)
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (2, 2)])
@@ -129,8 +97,7 @@ def test_spatial_parallel_sfno_with_geometric_instance_norm_matches_serial(h, w)
     """normalization_layer="instance_norm_s2" under h x w parallelism: DistributedGeometricInstanceNormS2
     (makani/mpu/layer_norm.py:173-253: area-weighted local moments merged over the spatial group) against the serial
     GeometricInstanceNormS2 network, forward, input gradient and every parameter gradient"""
-    world = h * w
-    mp.spawn(_worker, args=(world, _free_port(), h, w, "instance_norm_s2"), nprocs=world, join=True)
+    launch(_worker, h * w, h, w, "instance_norm_s2", limit=240)
 
 
 @pytest.mark.parametrize("operator_type,separable", [("diagonal", False), ("diagonal", True), ("dhconv", True)],
@@ -142,7 +109,7 @@ def test_spatial_parallel_sfno_other_operators_matches_serial(operator_type, sep
     ranks have a first degree that differs from their first order, tri_off = +6, 0, -6): the "diagonal" weight, dense and
     separable, is sharded over h AND w, so each rank's gradient is its window of the serial one with no reduction; the
     separable "dhconv" weight is shared over w like the dense one"""
-    mp.spawn(_worker, args=(4, _free_port(), 2, 2, "instance_norm", operator_type, separable, (12, 12)), nprocs=4, join=True)
+    launch(_worker, 4, 2, 2, "instance_norm", operator_type, separable, (12, 12), limit=240)
 
 
 class _OneRankTree:
@@ -166,16 +133,12 @@ class _OneRankTree:
         return True
 
 
-def _worker_rccl(rank, world, port):
+def _worker_rccl(rank, world, rendezvous):
     """RCCL itself on the one GPU of the box (world size 1): the collectives makani_amd.distributed.GradReducer issues —
     an async in-place all-reduce on the real view of a complex gradient, the flattened small-gradient bucket whose
     pieces become the gradients, and ReduceOp.AVG (or its fallback)."""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-    try:
+    with ranks(rank, world, rendezvous, "nccl", device=dev) as dist:
         import makani_amd.distributed as thd
         model = torch.nn.Module()
         model.c = torch.nn.Parameter(torch.randn(1200, 1024, dtype=torch.complex64, device=dev))     # 9.8 MB: async path
@@ -211,29 +174,20 @@ def _worker_rccl(rank, world, port):
         dp._exchange_async([out[0:2]], [big], dist.group.WORLD).wait()
         torch.cuda.synchronize()
         assert torch.equal(out.reshape(-1), big)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 def test_rccl_collectives_of_the_grad_reducer_world1():
-    mp.spawn(_worker_rccl, args=(1, _free_port()), nprocs=1, join=True)
+    launch(_worker_rccl, 1, limit=240)
 
 
-def _worker_ragged_gpu(rank, world, port, h, w, C, fused=True):
+def _worker_ragged_gpu(rank, world, rendezvous, h, w, C, fused=True):
     """BASELINE configs[2] / [4] split sizes at the real grid THROUGH THE HIP BACKEND: 721 x 1440, lmax 240, mmax 241 over
     h = 4 (lat [181, 181, 181, 178], l [60] * 4) and h4 w2 (lon [720, 720], m [121, 120]) with ragged plane counts; every
     rank's shard of the distributed transform and of its gradient against the serial HIP transform AND the fp64 oracle
     (split rule: makani/mpu/fft.py:50-51; tolerance of the reference's distributed tests: tests_distributed_layers.py:71-76)"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     torch.set_num_threads(4)
     os.environ["MAKANI_AMD_DIST_FUSED"] = "1" if fused else "0"
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # ranks sharing ONE GPU get disjoint compute units, set before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -288,36 +242,26 @@ def _worker_ragged_gpu(rank, world, port, h, w, C, fused=True):
                  "inv": (y, ys[sl_g], yo[sl_g]),
                  "inv_gc": (cl.grad.cpu() * tri, cfs.grad[sl_s].cpu() * tri, cfo.grad[sl_s] * tri)}
         for k, (a, b_hip, b_or) in pairs.items():
-            e1, e2 = _rel(torch.view_as_real(a.detach().cpu()) if a.is_complex() else a.detach().cpu(),
+            e1, e2 = rel(torch.view_as_real(a.detach().cpu()) if a.is_complex() else a.detach().cpu(),
                           torch.view_as_real(b_hip.detach().cpu()) if b_hip.is_complex() else b_hip.detach().cpu()), \
-                     _rel(torch.view_as_real(a.detach().cpu()) if a.is_complex() else a.detach().cpu(),
+                     rel(torch.view_as_real(a.detach().cpu()) if a.is_complex() else a.detach().cpu(),
                           torch.view_as_real(b_or.detach()) if b_or.is_complex() else b_or.detach())
             assert e1 < 1e-5 and e2 < 1e-5, (rank, k, e1, e2)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,C,fused", [(4, 1, 6, True), (4, 2, 5, True), (4, 2, 5, False), (2, 2, 48, True)])
 def test_distributed_sht_ragged_config3_splits_on_the_hip_backend(h, w, C, fused):
     """fused = the schedule of makani_amd/dist_pipeline.py (segmented FFT kernels, one h x w exchange, latitude-major Legendre
     operand, two latitude chunks); not fused = transpose by transpose"""
-    mp.spawn(_worker_ragged_gpu, args=(h * w, _free_port(), h, w, C, fused), nprocs=h * w, join=True)
+    launch(_worker_ragged_gpu, h * w, h, w, C, fused, limit=240)
 
 
 # --------------------------------------------------------------------------- #
 # BASELINE configs[4] as a composition: MultiStepWrapper (n_future = 3 = multistep_count 4) around the spatially parallel
 # network with the package's own gradient reduction — the reference's makani/models/stepper.py:224-284 over makani/mpu layers
 # --------------------------------------------------------------------------- #
-def _worker_multistep(rank, world, port, h, w, checkpointed, amp):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # ranks sharing ONE GPU get disjoint compute units, set before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_multistep(rank, world, rendezvous, h, w, checkpointed, amp):
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -347,8 +291,8 @@ def _worker_multistep(rank, world, port, h, w, checkpointed, amp):
             xs = x.clone().requires_grad_(True)
             ys = MultiStepWrapper(serial, n_future=NF).train()(xs)
             (ys * G).sum().backward()
-            e_ser = (_rel(y16, ys), _rel(gx16, xs.grad),
-                     max(_rel(_r(g16[k]), _r(p.grad)) for k, p in serial.named_parameters() if not k.endswith("mlp.fwd.3.bias")))
+            e_ser = (rel(y16, ys), rel(gx16, xs.grad),
+                     max(rel(_r(g16[k]), _r(p.grad)) for k, p in serial.named_parameters() if not k.endswith("mlp.fwd.3.bias")))
 
         _, ih, iw = mcomm.init(h, w)                       # the tree bench.py builds; the network finds h / w / spatial in it
         model = ma.SphericalFourierNeuralOperatorNet(**cfg).to(dev)
@@ -371,8 +315,8 @@ def _worker_multistep(rank, world, port, h, w, checkpointed, amp):
         # fp32: against the serial rollout; bf16: against the serial FP32 rollout, no further from it than 2 x the serial bf16
         # rollout is (a shard's relative error scatters around the whole field's)
         tol_y, tol_g = (2 * e_ser[0], 2 * e_ser[1]) if amp else (2e-4, 1e-3)
-        e_y = _rel(yl.float(), ys.float()[..., lat0:lat0 + hl, lon0:lon0 + wl])
-        e_gx = _rel(xl.grad, xs.grad[..., lat0:lat0 + hl, lon0:lon0 + wl])
+        e_y = rel(yl.float(), ys.float()[..., lat0:lat0 + hl, lon0:lon0 + wl])
+        e_gx = rel(xl.grad, xs.grad[..., lat0:lat0 + hl, lon0:lon0 + wl])
         assert e_y < tol_y and e_gx < tol_g, (rank, e_y, e_gx, e_ser)
         sref = dict(serial.named_parameters())
         for k, p in model.named_parameters():
@@ -382,12 +326,9 @@ def _worker_multistep(rank, world, port, h, w, checkpointed, amp):
             if amp or k.endswith("mlp.fwd.3.bias"):
                 continue
             ref = sref[k].grad[..., l0:l0 + ll] if k.endswith("filter.filter.weight") else sref[k].grad
-            e = _rel(torch.view_as_real(p.grad) if p.grad.is_complex() else p.grad,
+            e = rel(torch.view_as_real(p.grad) if p.grad.is_complex() else p.grad,
                      torch.view_as_real(ref.contiguous()) if ref.is_complex() else ref)
             assert e < tol_g, (rank, k, e)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,checkpointed,amp", [(2, 2, False, False), (2, 2, True, False), (2, 2, False, True), (4, 2, False, False)])
@@ -397,26 +338,21 @@ def test_multistep4_around_the_spatially_parallel_network_matches_serial(h, w, c
     the package's gradient reduction hooks, N ranks on one GPU, against the same rollout of the serial HIP network: all four
     outputs, the input gradient through the rollout, every parameter gradient AFTER the reductions (so p.grad is what the
     optimizer would see), with and without rollout checkpointing, fp32 and bf16 autocast"""
-    world = h * w
-    mp.spawn(_worker_multistep, args=(world, _free_port(), h, w, checkpointed, amp), nprocs=world, join=True)
+    launch(_worker_multistep, h * w, h, w, checkpointed, amp, limit=240)
 
 
 # --------------------------------------------------------------------------- #
 # the fused schedule's collectives on RCCL itself (one rank): VERDICT r3 item 5a
 # --------------------------------------------------------------------------- #
-def _worker_rccl_fused(rank, world, port):
+def _worker_rccl_fused(rank, world, rendezvous):
     """MAKANI_AMD_DIST_FORCE_FUSED=1 with h = w = 1 on the RCCL backend: the distributed transforms run the FUSED pipeline
     (segmented FFT kernels writing per-peer slabs, the list all_to_all(async_op=True) on contiguous slab views per latitude
     chunk, the waits that order the compute stream behind RCCL's stream, the latitude-major Legendre GEMMs) with a process
     group of one rank — the call signatures, view contiguity and stream ordering the first multi-GPU run will meet —
     against the serial HIP transform, forward and gradients, fp32 and bf16 input, full size 721 x 1440 included"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ["MAKANI_AMD_DIST_FORCE_FUSED"] = "1"
     dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
-    try:
+    with ranks(rank, world, rendezvous, "nccl", device=dev):
         import makani_amd as ma
         import makani_amd.distributed as thd
         from makani_amd import dist_pipeline as dp
@@ -445,29 +381,24 @@ def _worker_rccl_fused(rank, world, port):
             torch.cuda.synchronize()
             assert thd.COMM_STATS and sum(v["all_to_alls"] for v in thd.COMM_STATS.values()) >= 4      # the collectives were issued
             for k, (a, b) in enumerate(zip(*res)):
-                e = _rel(torch.view_as_real(a.cpu()) if a.is_complex() else a.cpu(), torch.view_as_real(b.cpu()) if b.is_complex() else b.cpu())
+                e = rel(torch.view_as_real(a.cpu()) if a.is_complex() else a.cpu(), torch.view_as_real(b.cpu()) if b.is_complex() else b.cpu())
                 assert e < (1e-5 if dt == torch.float32 else 1e-2), (nlat, nlon, k, e)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 def test_fused_schedule_collectives_on_rccl_world1():
-    mp.spawn(_worker_rccl_fused, args=(1, _free_port()), nprocs=1, join=True)
+    launch(_worker_rccl_fused, 1, limit=240)
 
 
 # --------------------------------------------------------------------------- #
 # hipGraph capture of the distributed step's building blocks WITH their RCCL collectives (one rank): what bench.py does for the
 # h x w step at N > 1 (the eager h4 w2 step is bound by the host: tools/shadow_rank.py, profiles/r05_shard_shapes.md)
 # --------------------------------------------------------------------------- #
-def _worker_rccl_graph(rank, world, port):
+def _worker_rccl_graph(rank, world, rendezvous):
     """one captured "step" on the RCCL backend with a process group of one rank: forward + backward of the FUSED distributed
     SHT pair (segmented FFT kernels, the list all_to_all(async_op=True) per latitude chunk, its waits), of the distributed
     instance norm (all_gather of the statistics, all_reduce of the backward sums, no host read after the first call) and the
     gradient reduction hooks (async all_reduce issued from post-accumulate hooks, finished by the autograd engine's
     callback) — captured once with torch.cuda.graph, replayed twice on fresh inputs, against the eager results"""
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     os.environ["MAKANI_AMD_DIST_FORCE_FUSED"] = "1"
     # torch 2.10's process group hands the work of a CAPTURED send / recv collective to its watchdog thread, whose event query
     # then fails ("operation not permitted on an event last recorded in a capturing stream") and, by default, takes the process
@@ -475,8 +406,7 @@ def _worker_rccl_graph(rank, world, port):
     os.environ["TORCH_NCCL_RETHROW_CUDA_ERRORS"] = "0"
     os.environ["TORCH_NCCL_ENABLE_MONITORING"] = "0"
     dev = torch.device("cuda:0")
-    torch.cuda.set_device(dev)
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    join_group(rank, world, rendezvous, "nccl", device=dev)
     try:
         import makani_amd.distributed as thd
         from makani_amd import dist_pipeline as dp
@@ -551,4 +481,4 @@ def _worker_rccl_graph(rank, world, port):
 
 
 def test_hipgraph_capture_of_the_distributed_blocks_with_rccl_world1():
-    mp.spawn(_worker_rccl_graph, args=(1, _free_port()), nprocs=1, join=True)
+    launch(_worker_rccl_graph, 1, limit=240)

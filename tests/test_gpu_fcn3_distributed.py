@@ -5,58 +5,14 @@ tests/distributed/tests_distributed_layers.py and tests_distributed_model.py; to
 compare with the serial operator the same way)."""
 import json
 import os
-import socket
-import sys
 
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import hw_groups, launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
-
-
-def _spawn(fn, nprocs, *args):
-    """mp.spawn with a fresh rendezvous port; one retry when another process grabbed the port between probing and binding"""
-    for attempt in (0, 1):
-        try:
-            mp.spawn(fn, args=(nprocs, _free_port()) + args, nprocs=nprocs, join=True)
-            return
-        except Exception as e:
-            if attempt == 1 or "EADDRINUSE" not in str(e):
-                raise
-
-
-def _setup(rank, world, port, h, w):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # ranks sharing ONE GPU get disjoint compute units, set before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    ih, iw = rank // w, rank % w
-    hg = wg = None
-    for j in range(w):
-        g = dist.new_group([i * w + j for i in range(h)])
-        if j == iw:
-            hg = g
-    for i in range(h):
-        g = dist.new_group([i * w + j for j in range(w)])
-        if i == ih:
-            wg = g
-    return ih, iw, hg, wg
 
 
 def _shard(t, lat_shapes, lon_shapes, ih, iw):
@@ -64,9 +20,9 @@ def _shard(t, lat_shapes, lon_shapes, ih, iw):
     return t[..., a:a + lat_shapes[ih], b:b + lon_shapes[iw]]
 
 
-def _worker_ops(rank, world, port, h, w):
-    ih, iw, hg, wg = _setup(rank, world, port, h, w)
-    try:
+def _worker_ops(rank, world, rendezvous, h, w):
+    with ranks(rank, world, rendezvous) as dist:
+        ih, iw, hg, wg = hw_groups(rank, h, w)
         import makani_amd.distributed as thd
         from makani_amd import disco
         dev = torch.device("cuda:0")
@@ -108,33 +64,30 @@ def _worker_ops(rank, world, port, h, w):
             assert yl.shape == gl.shape, (yl.shape, gl.shape)
             (yl * gl).sum().backward()
             tol = 2e-2 if c["dtype"] == torch.bfloat16 else 2e-6
-            e_y = _rel(yl, _shard(y, d.lat_out_shapes, d.lon_out_shapes, ih, iw))
-            e_x = _rel(xl.grad, _shard(x.grad, d.lat_in_shapes, d.lon_in_shapes, ih, iw))
+            e_y = rel(yl, _shard(y, d.lat_out_shapes, d.lon_out_shapes, ih, iw))
+            e_x = rel(xl.grad, _shard(x.grad, d.lat_in_shapes, d.lon_in_shapes, ih, iw))
             assert e_y < tol and e_x < tol, (rank, c, e_y, e_x)
             for k, p in d.named_parameters():
                 gp = p.grad.detach().float().cpu()
                 dist.all_reduce(gp)                                   # replicated weight: shard gradients sum
-                e = _rel(gp, dict(m.named_parameters())[k].grad.float().cpu())
+                e = rel(gp, dict(m.named_parameters())[k].grad.float().cpu())
                 assert e < (3e-2 if c["dtype"] == torch.bfloat16 else 1e-5), (rank, k, e)
         dr = disco.DistributedResampleS2(17, 32, 33, 64, grid_in="legendre-gauss", grid_out="equiangular").to(dev)
         xl = _shard(xr.detach(), dr.lat_in_shapes, dr.lon_in_shapes, ih, iw).clone().requires_grad_(True)
         yl = dr(xl)
         (yl * _shard(gr, dr.lat_out_shapes, dr.lon_out_shapes, ih, iw)).sum().backward()
-        assert _rel(yl, _shard(yr, dr.lat_out_shapes, dr.lon_out_shapes, ih, iw)) < 1e-6
-        assert _rel(xl.grad, _shard(xr.grad, dr.lat_in_shapes, dr.lon_in_shapes, ih, iw)) < 1e-6
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
+        assert rel(yl, _shard(yr, dr.lat_out_shapes, dr.lon_out_shapes, ih, iw)) < 1e-6
+        assert rel(xl.grad, _shard(xr.grad, dr.lat_in_shapes, dr.lon_in_shapes, ih, iw)) < 1e-6
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2), (3, 1)])
 def test_distributed_disco_and_resample_match_serial(h, w):
-    _spawn(_worker_ops, h * w, h, w)
+    launch(_worker_ops, h * w, h, w, limit=240)
 
 
-def _worker_fcn3(rank, world, port, h, w, name):
-    ih, iw, hg, wg = _setup(rank, world, port, h, w)
-    try:
+def _worker_fcn3(rank, world, rendezvous, h, w, name):
+    with ranks(rank, world, rendezvous) as dist:
+        ih, iw, hg, wg = hw_groups(rank, h, w)
         import numpy as np
         import makani_amd as ma
         import makani_amd.distributed as thd
@@ -167,8 +120,8 @@ def _worker_fcn3(rank, world, port, h, w, name):
         xl = _shard(x, lat, lon, ih, iw).clone().requires_grad_(True)
         yl = model(xl)
         (yl * _shard(G, lat, lon, ih, iw)).sum().backward()
-        e_y = _rel(yl, _shard(ys, lat, lon, ih, iw))
-        e_gx = _rel(xl.grad, _shard(xs.grad, lat, lon, ih, iw))
+        e_y = rel(yl, _shard(ys, lat, lon, ih, iw))
+        e_gx = rel(xl.grad, _shard(xs.grad, lat, lon, ih, iw))
         assert e_y < 1e-4 and e_gx < 2e-4, (rank, e_y, e_gx)
         sref = dict(serial.named_parameters())
         gmax = max(float(p.grad.abs().max()) for p in sref.values())
@@ -182,14 +135,11 @@ def _worker_fcn3(rank, world, port, h, w, name):
             else:
                 dist.all_reduce(gp)
                 ref = sref[k].grad.cpu()
-            e, a = _rel(gp, ref), (gp - ref).abs().max().item()
+            e, a = rel(gp, ref), (gp - ref).abs().max().item()
             assert e < 5e-4 or a < 1e-4 * gmax, (rank, k, e, a)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,name", [(2, 1, "fcn3_small_33x64.npz"), (1, 2, "fcn3_small_33x64.npz"),
                                       (2, 2, "fcn3_small_33x64.npz"), (2, 2, "fcn3_options_24x48.npz")])
 def test_spatial_parallel_fcn3_matches_serial(h, w, name):
-    _spawn(_worker_fcn3, h * w, h, w, name)
+    launch(_worker_fcn3, h * w, h, w, name, limit=240)

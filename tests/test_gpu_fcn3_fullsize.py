@@ -9,26 +9,19 @@ shards and 720-column longitude shards, the distributed bilinear resampling 721 
 Reference twins: tests/distributed/tests_distributed_model.py:218-330, makani/models/networks/fourcastnet3.py:339-381.
 Tolerance: fp32 <= 1e-4 end to end (tests/distributed/tests_distributed_layers.py:71-76)."""
 import os
-import socket
 import sys
 import time
 
 import pytest
 import torch
-import torch.distributed as dist
 
-from _fullsize import CACHE_DIR, log_line, spawn
+from _fullsize import CACHE_DIR, log_line
+from _ranks import launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-4
 H, W = 2, 2
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _r(t):
@@ -38,10 +31,10 @@ def _r(t):
     return t
 
 
-def _rel(a, b):
-    a, b = _r(a).cpu().double(), _r(b).cpu().double()
+def _rel_real(a, b):
+    a, b = _r(a).cpu(), _r(b).cpu()
     assert a.shape == b.shape, (a.shape, b.shape)
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
+    return rel(a, b)
 
 
 def _config():
@@ -50,8 +43,8 @@ def _config():
     return bench.FCN3_CONFIGS["fcn3_sc2_edim45_layers10"]["model"], bench.CONFIGS["fcn3_sc2_edim45_layers10"]
 
 
-def _serial_worker(rank, path):
-    """the SERIAL HIP network in a process of its own (its ~100 GB of fp32 activations are gone when it ends)"""
+def _serial_worker(rank, world, rendezvous, path):
+    """the SERIAL HIP network in a process of its own (its ~100 GB of fp32 activations are gone when it ends); it joins no group"""
     sys.path.insert(0, ROOT)
     os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
     import makani_amd as ma
@@ -77,7 +70,7 @@ def _serial_worker(rank, path):
 @pytest.fixture(scope="module")
 def serial_fcn3():
     path = os.path.join(CACHE_DIR, f"fcn3_hip_serial_{os.getpid()}.pt")
-    spawn(_serial_worker, (path,), 1, timeout_s=900)
+    launch(_serial_worker, 1, path, limit=900)
     d = torch.load(path, mmap=True, weights_only=True)
     log_line(f"--- FourCastNet3 fcn3_sc2_edim45_layers10 serial HIP fp32 forward + backward at 721x1440: peak {float(d['peak_gib']):.1f} GiB, "
              f"{float(d['seconds']):.1f} s ---")
@@ -93,14 +86,9 @@ def _shard(t, lat, lon, ih, iw):
     return t[..., a:a + lat[ih], b:b + lon[iw]]
 
 
-def _worker(rank, world, port, path):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
+def _worker(rank, world, rendezvous, path):
     torch.set_num_threads(8)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -130,8 +118,8 @@ def _worker(rank, world, port, path):
         (yl * gl).sum().backward()
         torch.cuda.synchronize()
         t2 = time.time()
-        e_y = _rel(yl, _shard(ref["y"], lat, lon, ih, iw))
-        e_gx = _rel(xl.grad, _shard(ref["gx"], lat, lon, ih, iw))
+        e_y = _rel_real(yl, _shard(ref["y"], lat, lon, ih, iw))
+        e_gx = _rel_real(xl.grad, _shard(ref["gx"], lat, lon, ih, iw))
         gmax = max(float(v.abs().max()) for v in ref["grads"].values())
         hgrp, wgrp = mcomm.get_group("h") if H > 1 else None, mcomm.get_group("w") if W > 1 else None
         worst, bad = ("", 0.0), {}
@@ -145,7 +133,7 @@ def _worker(rank, world, port, path):
             else:                                                    # replicated: the shards' gradients sum over h x w
                 dist.all_reduce(gp)
                 r = ref["grads"][k]
-            e, a = _rel(gp, r), float((gp.double() - r.double()).abs().max())
+            e, a = _rel_real(gp, r), float((gp.double() - r.double()).abs().max())
             if not (e < TOL or a < 1e-5 * gmax):
                 bad[k] = (e, a)
             if e > worst[1] and a >= 1e-5 * gmax:
@@ -156,11 +144,8 @@ def _worker(rank, world, port, path):
                  f"fwd+bwd over gloo {t2 - t1:.1f} s")
         assert e_y < TOL and e_gx < TOL, (rank, e_y, e_gx)
         assert not bad, (rank, bad)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 def test_fcn3_fullsize_h2w2_fwd_bwd_matches_serial(serial_fcn3):
     log_line("--- test_fcn3_fullsize_h2w2_fwd_bwd_matches_serial: fcn3_sc2_edim45_layers10, 721x1440 / 360x720 / 677 ch, 4 ranks on one GPU ---")
-    spawn(_worker, (H * W, _free_port(), serial_fcn3), H * W, timeout_s=1500)
+    launch(_worker, H * W, serial_fcn3, limit=1500)

@@ -5,31 +5,14 @@ Everything but the noise is pointwise in space, and the noise of ranks that shar
 rank's 2-step sample is the slice of the serial sample within the relative 1e-5 that test_gpu_noise_dist.py uses for synthesised
 fields.  Grid 37 x 72, h = 2: the latitudes split [19, 18].  The generator of the interpolant times is seeded without the
 model-rank term, so both ranks would draw the same s.  Each process runs under its own time limit; a failing rank ends the test."""
-import os
-import socket
-import sys
-import time
-
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG, B, C, U, ST = (37, 72), 2, 3, 2, 2
 TOL = 1e-5
-LIMIT = 240.0          # seconds per process, far above the few seconds a rank needs
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
 
 class _Params(dict):
@@ -58,15 +41,8 @@ def _build(ma, static, foellmer):
     return ma.StochasticInterpolantWrapper.from_params(params, handle, noise_epsilon=0.7, use_foellmer=foellmer, seed=41, static_features=static)
 
 
-def _worker(rank, world, port, h, w):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker(rank, world, rendezvous, h, w):
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -103,22 +79,11 @@ def _worker(rank, world, port, h, w):
             assert mod._rng_seed == serial[f]._rng_seed == 41 + 333          # no model-rank term: the ranks draw the same s
             y = sample(mod, grid)
             assert tuple(y.shape) == (B, C, probe.nlat_local, probe.nlon_local) and bool(want[f][grid].abs().max() > 1e-3)
-            e = _rel(y, want[f][grid])
+            e = rel(y, want[f][grid])
             print(f"h{h}w{w} rank {rank} foellmer {f}: sample rel {e:.1e}", flush=True)
             assert e < TOL, (rank, f, e)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 def test_split_sampler_gives_the_slices_of_the_serial_sample():
     h, w = 2, 1
-    ctx = mp.spawn(_worker, args=(h * w, _free_port(), h, w), nprocs=h * w, join=False)
-    deadline = time.monotonic() + LIMIT
-    try:
-        while not ctx.join(timeout=max(0.1, deadline - time.monotonic())):          # raises when a rank failed, and ends the others
-            assert time.monotonic() < deadline, f"a rank ran into its time limit of {LIMIT:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
+    launch(_worker, h * w, h, w, limit=240)          # far above the few seconds a rank needs

@@ -9,16 +9,12 @@ time limit each.
 
 The scalar is the same on every rank and within 1e-5 of the serial one; the gradient of this rank's shard / members is within
 1e-5 (rel-L2) of the slice of the serial gradient.  RCCL with more than one GPU is not exercised here."""
-import os
-import socket
-import sys
-import time
-
 import pytest
 import torch
 
+from _ranks import launch, ranks, rel
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG, B, NH = (17, 32), 2, 1
 NAMES = "u10m t2m z500 z850 z1000 t500 t850 t1000 q500 q850 q1000".split()
 C = len(NAMES)
@@ -26,10 +22,6 @@ L2 = {"type": "l2", "channel_weights": "auto", "temp_diff_normalization": True}
 CRPS = {"type": "ensemble_crps", "relative_weight": 0.5}
 DRIFT = {"type": "drift_regularization", "parameters": {"p": 2}}
 HYDRO = {"type": "hydrostatic", "parameters": {"p_min": 400, "use_moist_air_formula": True}, "relative_weight": 1e-4}
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
 
 def _stats():
@@ -56,7 +48,6 @@ def _tensors(E):
 
 def _run(ma, losses, t, cut, members, dev):
     """scalar and gradient of a handler built under the process groups as they are now, on the cut tensors"""
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     from _losshandler_ref import Params
     bias, scale, tds = _stats()
     params = Params(n_future=0, n_history=NH, img_shape_x_resampled=IMG[0], img_shape_y_resampled=IMG[1], img_crop_offset_x=0,
@@ -68,19 +59,6 @@ def _run(ma, losses, t, cut, members, dev):
     return h, loss.detach(), grad
 
 
-def _setup(rank, world, port):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    return dist
-
-
 def _same_on_every_rank(dist, world, loss):
     mine = loss.cpu().reshape(1)
     every = [torch.empty_like(mine) for _ in range(world)]
@@ -88,9 +66,8 @@ def _same_on_every_rank(dist, world, loss):
     assert all(torch.equal(e, every[0]) for e in every), "the scalar differs between ranks"
 
 
-def _worker_spatial(rank, world, port):
-    dist = _setup(rank, world, port)
-    try:
+def _worker_spatial(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -108,17 +85,13 @@ def _worker_spatial(rank, world, port):
         hd, got, ggot = _run(ma, losses, t, cut, slice(None), dev)
         assert hd.spatial_distributed and all(getattr(f, "spatial_distributed") for f in hd.loss_fn)
         _same_on_every_rank(dist, world, got)
-        errs = dict(loss=_rel(got, want), grad=_rel(ggot, gwant[cut]))
+        errs = dict(loss=rel(got, want), grad=rel(ggot, gwant[cut]))
         print(f"h2w2 rank {rank}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()), flush=True)
         assert max(errs.values()) <= 1e-5, (rank, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_ensemble(rank, world, port):
-    dist = _setup(rank, world, port)
-    try:
+def _worker_ensemble(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = torch.device("cuda:0")
@@ -133,34 +106,14 @@ def _worker_ensemble(rank, world, port):
         hd, got, ggot = _run(ma, losses, t, full, members, dev)
         assert hd.ensemble_distributed and mcomm.get_size("ensemble") == 2
         _same_on_every_rank(dist, world, got)
-        errs = dict(loss=_rel(got, want), grad=_rel(ggot, gwant[:, members]))
+        errs = dict(loss=rel(got, want), grad=rel(ggot, gwant[:, members]))
         print(f"ensemble rank {rank}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()), flush=True)
         assert max(errs.values()) <= 1e-5, (rank, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _spawn(worker, world, limit):
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(worker, args=(world, port), nprocs=world, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
+def test_h2_w2_shards_equal_the_serial_handler():
+    launch(_worker_spatial, 4, limit=240)
 
 
-def test_h2_w2_shards_equal_the_serial_handler(limit=240.0):
-    _spawn(_worker_spatial, 4, limit)
-
-
-def test_ensemble_group_of_two_equals_the_serial_handler(limit=240.0):
-    _spawn(_worker_ensemble, 2, limit)
+def test_ensemble_group_of_two_equals_the_serial_handler():
+    launch(_worker_ensemble, 2, limit=240)

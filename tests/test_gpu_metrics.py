@@ -19,15 +19,12 @@ restatement on them — test_inputs_let_the_fp32_formula_meet_the_tolerance asse
     rounded value, which the kernel sees).
 fp32 torch formula against the restatement on these inputs, worst case over the cases (relative L2 per output; bins per entry):
   deterministic sums 8.6e-08,  skill 6.6e-08,  spread 7.4e-08,  occupied bins 1.6e-07 (empty bins exactly 0)."""
-import os
-import sys
-import time
-
 import pytest
 import torch
 import torch.nn.functional as F
 
 import _metrics_ref as ref
+from _ranks import launch, ranks
 from conftest import load_golden
 
 GRIDS = [(17, 32), (9, 14), (91, 180)]
@@ -35,7 +32,6 @@ B, C = 2, 3
 ES = [1, 2, 3, 8, 9, 32]
 TOL = 1e-5
 f32, bf16 = torch.float32, torch.bfloat16
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (grid, x dtype, y dtype, weight, bias)
 DET_CASES = ([(2, dx, dy, True, True) for dx in (f32, bf16) for dy in (f32, bf16)]
@@ -342,43 +338,10 @@ def test_a_deterministic_and_an_ensemble_call_replay_from_a_captured_graph():
 
 
 # ---- several processes on one GPU ---------------------------------------------------------------------------------------
-def _spawn(fn, world, limit=240.0):
-    """``mp.spawn`` under ONE time limit: the first failing rank ends the others (``ProcessContext.join``), and so does the limit"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(fn, args=(world, port), nprocs=world, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"{fn.__name__}: the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
-
-
-def _setup(rank, world, port):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    return dist
-
-
-def _worker_ensemble(rank, world, port):
+def _worker_ensemble(rank, world, rendezvous):
     """two ensemble ranks, four members each: SSR and rank histogram with ensemble_distributed=True, Spread as it is (it follows
     the group), against the serial modules (built before the tree exists) on the gathered ensemble"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -403,16 +366,12 @@ def _worker_ensemble(rank, world, port):
                 err = ref.mismatch(out, want)
                 print(f"rank {rank} {cls} weights {wt is not None}: {err:.2e}", flush=True)
                 assert out.shape == want.shape and err < TOL, (cls, err)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_spatial(rank, world, port):
+def _worker_spatial(rank, world, rendezvous):
     """h2 x w2 on a 37 x 72 grid (19 + 18 latitudes): all seven classes with spatial_distributed=True on the local shard, ACC
     with a climatology (cut to the shard by the constructor), against the serial modules on the whole grid"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         from makani_amd import distributed as thd
@@ -447,16 +406,13 @@ def _worker_spatial(rank, world, port):
             err = ref.mismatch(out, wnt)
             print(f"rank {rank} (h {ih}, w {iw}) {cls} {extra.get('method', '')}: {err:.2e}", flush=True)
             assert out.shape == wnt.shape and err < TOL, (cls, err)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.gpu
 def test_ensemble_parallel_metrics_match_serial():
-    _spawn(_worker_ensemble, 2)
+    launch(_worker_ensemble, 2, limit=240)
 
 
 @pytest.mark.gpu
 def test_spatially_parallel_metrics_match_serial():
-    _spawn(_worker_spatial, 4)
+    launch(_worker_spatial, 4, limit=240)

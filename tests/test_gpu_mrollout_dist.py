@@ -10,31 +10,14 @@ tests/_mrollout_cases.py, three ``idt`` rows.
 * an "ensemble" group of two, E = 4: every rank holds two members and takes the composed path, against the serial handler with
   all four.
 RCCL with more than one GPU is not exercised here."""
-import os
-import socket
-import sys
-import time
-
 import pytest
 import torch
 
+from _ranks import launch, ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 1e-5
 GRID = 1          # 17 x 32
-
-
-def _setup(rank, world, port):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    return dist
 
 
 def _handler(ma, E, dev):
@@ -81,9 +64,8 @@ def _same_on_every_rank(dist, world, t):
     assert all(torch.equal(e, every[0]) for e in every), "the buffers differ between ranks"
 
 
-def _worker_spatial(rank, world, port):
-    dist = _setup(rank, world, port)
-    try:
+def _worker_spatial(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -109,14 +91,10 @@ def _worker_spatial(rank, world, port):
         _same_on_every_rank(dist, world, h._flat)
         gathered = h._gather_input(cases.call_inputs(key, 0)[1][cut].contiguous().to(dev))
         assert torch.equal(gathered.cpu(), cases.call_inputs(key, 0)[1])
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_batch(rank, world, port):
-    dist = _setup(rank, world, port)
-    try:
+def _worker_batch(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import _mrollout_cases as cases
@@ -138,14 +116,10 @@ def _worker_batch(rank, world, port):
         assert logs["base"] == want["base"] and list(logs["metrics"]) == list(want["metrics"])
         assert bool((h._by_name["L1"].rollout_counter == 2.0).all())
         _same_on_every_rank(dist, world, h._flat)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_ensemble(rank, world, port):
-    dist = _setup(rank, world, port)
-    try:
+def _worker_ensemble(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import _mrollout_cases as cases
@@ -163,35 +137,15 @@ def _worker_ensemble(rank, world, port):
         errs = _errors(h, serial)
         print(f"ensemble rank {rank}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()), flush=True)
         assert max(errs.values()) <= TOL, (rank, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _spawn(worker, world, limit):
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(worker, args=(world, port), nprocs=world, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
+def test_h2_w2_shards_equal_the_serial_handler():
+    launch(_worker_spatial, 4, limit=240)
 
 
-def test_h2_w2_shards_equal_the_serial_handler(limit=240.0):
-    _spawn(_worker_spatial, 4, limit)
+def test_a_batch_group_of_two_reduces_to_the_serial_handler():
+    launch(_worker_batch, 2, limit=240)
 
 
-def test_a_batch_group_of_two_reduces_to_the_serial_handler(limit=240.0):
-    _spawn(_worker_batch, 2, limit)
-
-
-def test_an_ensemble_group_of_two_takes_the_composed_path_and_equals_serial(limit=240.0):
-    _spawn(_worker_ensemble, 2, limit)
+def test_an_ensemble_group_of_two_takes_the_composed_path_and_equals_serial():
+    launch(_worker_ensemble, 2, limit=240)

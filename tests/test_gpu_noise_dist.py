@@ -6,29 +6,14 @@ are compared with the serial module's state by torch.equal, the synthesised fiel
 test_distributed_sht_ragged_config3_splits_on_the_hip_backend (the reference's own tolerance for its distributed layers).
 Grid 37 x 72, lmax = mmax = 37: over two ranks l, m and the latitudes split [19, 18] (ragged, and m0 = 19 is odd: the second w
 rank's floats start in the middle of a Philox group), the longitudes [36, 36]."""
-import os
-import socket
-import sys
-
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import launch, ranks, rel
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG, B, C = (37, 72), 2, 3
 TOL = 1e-5
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
 
 def _build(ma):
@@ -52,15 +37,8 @@ def _run(m):
     return out
 
 
-def _worker(rank, world, port, h, w):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker(rank, world, rendezvous, h, w):
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -106,7 +84,7 @@ def _worker(rank, world, port, h, w):
             for stage, ((state, field), (wstate, wfield)) in enumerate(zip(_run(m), want[k])):
                 assert bool(state.any()) and torch.equal(state, wstate[spec]), (rank, k, stage, "state")
                 assert tuple(field.shape) == (B, m.num_time_steps, C, hl, wl) and bool(wfield[grid].abs().max() > 1e-3)
-                e = _rel(field, wfield[grid])
+                e = rel(field, wfield[grid])
                 print(f"h{h}w{w} rank {rank} {k} stage {stage}: field rel {e:.1e}", flush=True)
                 assert e < TOL, (rank, k, stage, e)
             assert m.rng.tolist() == s.rng.tolist()
@@ -127,8 +105,8 @@ def _worker(rank, world, port, h, w):
         assert torch.equal(ml_.state, sl.state[spec])
         (grad,) = torch.autograd.grad((ml_() * G[grid]).sum(), ml_.sigma_l)
         tri = torch.tril(torch.ones(37, 37, device=dev))[l0:l0 + ll, mo:mo + ml]
-        e = _rel(grad * tri, want_grad[..., l0:l0 + ll, mo:mo + ml] * tri)
-        print(f"h{h}w{w} rank {rank} sigma_l gradient rel {e:.1e} (all entries: {_rel(grad, want_grad[..., l0:l0 + ll, mo:mo + ml]):.1e})",
+        e = rel(grad * tri, want_grad[..., l0:l0 + ll, mo:mo + ml] * tri)
+        print(f"h{h}w{w} rank {rank} sigma_l gradient rel {e:.1e} (all entries: {rel(grad, want_grad[..., l0:l0 + ll, mo:mo + ml]):.1e})",
               flush=True)
         assert e < TOL and bool(want_grad.abs().max() > 1e-3), (rank, "sigma_l gradient", e)        # (a shard may lie wholly in m > l)
 
@@ -145,13 +123,10 @@ def _worker(rank, world, port, h, w):
         fresh.update()
         assert torch.equal(fresh.state, m.state) and fresh.rng.tolist() == m.rng.tolist() == [12, 6]
         torch.backends.cuda.matmul.allow_tf32 = was
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w", [(2, 1), (1, 2), (2, 2)])
 def test_noise_shards_equal_the_serial_state_and_field(h, w):
     """DiffusionNoiseS2 (T = 1, 2), IsotropicGaussianRandomFieldS2 (fixed and learnable) and DummyNoiseS2 under h x w: states,
     sigma_l shards, fields, the sigma_l gradient and a save / restore, every rank against the serial module of the same seed"""
-    mp.spawn(_worker, args=(h * w, _free_port(), h, w), nprocs=h * w, join=True)
+    launch(_worker, h * w, h, w, limit=240)

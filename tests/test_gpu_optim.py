@@ -2,37 +2,20 @@
 ZeRO-1 (reduce-scattered gradients, sharded AdamW state, parameter all-gather: SURVEY.md §8f item 3) with N ranks sharing
 cuda:0 over gloo against single-process torch.optim.AdamW, and the checkpoint round trip of the device-side step counter
 (makani loads checkpoints with map_location="cpu": makani/utils/driver.py:436,507)."""
-import os
-import socket
-import sys
-
 import pytest
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
+
+from _ranks import launch, ranks
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 def _r(t):
     return torch.view_as_real(t) if t.is_complex() else t
 
 
-def _worker_zero_gpu(rank, world, port):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # ranks sharing ONE GPU get disjoint compute units, set before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _worker_zero_gpu(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous):
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
         import makani_amd.optim as mo
@@ -92,14 +75,11 @@ def _worker_zero_gpu(rank, world, port):
         assert opt.state[model.w]["exp_avg"].numel() == 1536 * 1024 // world
         assert opt.state[model.n]["exp_avg"].numel() == 2 * 64 * 48 * 120 // world
         assert opt.state[model.odd]["exp_avg"].numel() == 1048583
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_zero1_on_the_hip_kernels_matches_single_process_adamw(world):
-    mp.spawn(_worker_zero_gpu, args=(world, _free_port()), nprocs=world, join=True)
+    launch(_worker_zero_gpu, world, limit=240)
 
 
 @pytest.mark.parametrize("source", ["fused", "torch"])

@@ -6,16 +6,12 @@ statistics of every rank equal each other bit for bit (merged in rank order from
 the serial ones; output shards and window- / noise-gradient shards are within 1e-5 of the slices of the serial result.  The loss
 sum(out r1) + sum(finish(yn) r2) sends a gradient to the statistics on every rank, so backward all-reduces the partials of G.
 RCCL with more than one GPU is not exercised here."""
-import os
-import socket
-import sys
-import time
-
 import pytest
 import torch
 
+from _ranks import launch, ranks, rel
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG, B, C, U, N, S, NH = (19, 36), 2, 3, 2, 1, 2, 1
 T = NH + 1
 
@@ -33,10 +29,6 @@ class _ParamNoise(torch.nn.Module):
 
     def is_stateful(self):
         return False
-
-
-def _rel(a, b):
-    return ((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30)).item()
 
 
 def _tensors():
@@ -66,17 +58,8 @@ def _run(ma, t, cut, dev, distributed):
     return dict(out=out.detach(), mean=pre.history_mean.detach(), std=pre.history_std.detach(), y=y.detach(), gwin=gwin, gnoi=gnoi)
 
 
-def _worker(rank, world, port):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    try:
+def _worker(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -96,29 +79,13 @@ def _worker(rank, world, port):
         every = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(every, mine)
         assert all(torch.equal(e, every[0]) for e in every), "the statistics differ between ranks"
-        errs = dict(mean=_rel(got["mean"], want["mean"]), std=_rel(got["std"], want["std"]))
+        errs = dict(mean=rel(got["mean"], want["mean"]), std=rel(got["std"], want["std"]))
         assert max(errs.values()) <= 1e-6, (rank, errs)
         for k in ("out", "y", "gwin", "gnoi"):
-            errs[k] = _rel(got[k], want[k][cut])
+            errs[k] = rel(got[k], want[k][cut])
             assert errs[k] <= 1e-5, (rank, k, errs[k])
         print(f"h2w2 rank {rank}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()), flush=True)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def test_h2_w2_shards_equal_the_serial_preprocessor(limit=240.0):
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(_worker, args=(4, port), nprocs=4, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
+def test_h2_w2_shards_equal_the_serial_preprocessor():
+    launch(_worker, 4, limit=240)

@@ -23,15 +23,13 @@ it, no GPU needed):
 fp32 torch formula against the restatement on these inputs, worst case over the cases of a loss (value / gradient):
   AMSE 1.1e-07 / 3.8e-07 (target gradient 4.9e-07),  NLL 7.8e-08 / 4.5e-07,  MMD 2.1e-07 / 2.9e-07."""
 import math
-import os
-import sys
-import time
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import _restloss_ref as ref
+from _ranks import launch, ranks
 from conftest import load_golden, rel_l2
 
 IMG, NAMES = (91, 180), ["u500", "v500", "t2m"]
@@ -41,7 +39,6 @@ TOL = 1e-5
 KW = dict(img_shape=IMG, crop_shape=IMG, crop_offset=(0, 0), channel_names=NAMES, grid_type="equiangular")
 AMSE_GRIDS = [(47, 92), (91, 180)]          # legendre-gauss: bandlimit nlat - 1 = 46 (a row shorter than a wave) and 90 (a wave and a tail)
 MMD_FORMS = [dict(sigma=80.0), dict(sigma=20.0, alpha=0.9, beta=1.0, channel_reduction=True)]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _smooth(n, gen, img=IMG):
@@ -304,43 +301,10 @@ def test_forward_and_backward_replay_from_a_captured_graph(key):
 
 
 # ---- several processes on one GPU ---------------------------------------------------------------------------------------
-def _spawn(fn, world, limit=240.0):
-    """``mp.spawn`` under ONE time limit: the first failing rank ends the others (``ProcessContext.join``), and so does the limit"""
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(fn, args=(world, port), nprocs=world, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"{fn.__name__}: the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
-
-
-def _setup(rank, world, port):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    return dist
-
-
-def _worker_ensemble(rank, world, port):
+def _worker_ensemble(rank, world, rendezvous):
     """two ensemble ranks, four members each: NLL and MMD with ensemble_distributed=True against the serial modules on the
     gathered ensemble (value) and its local members (gradient)"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -366,16 +330,12 @@ def _worker_ensemble(rank, world, port):
             errs = rel_l2(out, want), rel_l2(fl.grad, fs.grad[:, ie * El:(ie + 1) * El])
             print(f"rank {rank} {cls.__name__} {extra}: value {errs[0]:.2e} gradient {errs[1]:.2e}", flush=True)
             assert max(errs) < TOL, (cls.__name__, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _worker_spatial(rank, world, port):
+def _worker_spatial(rank, world, rendezvous):
     """h2 x w2: AMSE with spatial_distributed=True on a 37 x 72 grid (19 + 18 latitudes; the w rank 1 holds no order 0)
     against the serial module: value, and the local shards of prediction and target gradient"""
-    dist = _setup(rank, world, port)
-    try:
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         dev = "cuda:0"
@@ -407,16 +367,13 @@ def _worker_spatial(rank, world, port):
             errs = rel_l2(out, want), rel_l2(pl.grad, ps.grad[..., hs, ws]), rel_l2(tl.grad, ts.grad[..., hs, ws])
             print(f"rank {rank} (h {ih}, w {iw}) AMSE weights {use_w}: value {errs[0]:.2e} gradients {errs[1]:.2e} {errs[2]:.2e}", flush=True)
             assert max(errs) < TOL, errs
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 @pytest.mark.gpu
 def test_ensemble_parallel_nll_and_mmd_match_serial():
-    _spawn(_worker_ensemble, 2)
+    launch(_worker_ensemble, 2, limit=240)
 
 
 @pytest.mark.gpu
 def test_spatially_parallel_amse_matches_serial():
-    _spawn(_worker_spatial, 4)
+    launch(_worker_spatial, 4, limit=240)

@@ -8,30 +8,17 @@ longitudes [18, 18].
   serial one.
 * h2 w1: ``ZonalSpectrumAverageBuffer(spatial_distributed=True)`` equals the latitude slices of the serial buffer.
 RCCL with more than one GPU is not exercised here."""
-import os
-import socket
-import sys
-import time
-
 import pytest
 import torch
 
+from _ranks import launch, ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IMG, NCHAN, SELECTED, E = (19, 36), 5, ["c3", "c0"], 2
 
 
-def _worker(rank, world, port, h, w):
-    import datetime
-    import torch.distributed as dist
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)              # before the first GPU call
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=120))
-    try:
+def _worker(rank, world, rendezvous, h, w):
+    with ranks(rank, world, rendezvous, timeout=120) as dist:
         import _rollout_ref as R
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -98,31 +85,11 @@ def _worker(rank, world, port, h, w):
                 errs[f"zonal {name}"] = R.rel(g, s[..., rows, :])
         print(f"h{h}w{w} rank {rank}: " + " ".join(f"{k} {v:.1e}" for k, v in errs.items()), flush=True)
         assert max(errs.values()) <= 1e-5, (rank, errs)
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def _spawn(world, h, w, limit):
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ctx = mp.spawn(_worker, args=(world, port, h, w), nprocs=world, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
+def test_h2_w2_spectrum_shards_and_temporal_shards_equal_the_serial_buffers():
+    launch(_worker, 4, 2, 2, limit=240)
 
 
-def test_h2_w2_spectrum_shards_and_temporal_shards_equal_the_serial_buffers(limit=240.0):
-    _spawn(4, 2, 2, limit)
-
-
-def test_h2_w1_zonal_latitude_shards_equal_the_serial_buffer(limit=240.0):
-    _spawn(2, 2, 1, limit)
+def test_h2_w1_zonal_latitude_shards_equal_the_serial_buffer():
+    launch(_worker, 2, 2, 1, limit=240)

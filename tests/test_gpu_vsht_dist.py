@@ -6,28 +6,20 @@ the pattern of tests/test_gpu_noise_dist.py; RCCL with more than one rank has no
 import json
 import math
 import os
-import socket
-import sys
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 import _vsht_ref as ref
+from _ranks import launch, ranks
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "vsht_losses.npz")
 TOL = 1e-5            # tests/test_gpu_vsht.py: three limbs; two limbs (allow_tf32) 2e-5
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -128,16 +120,6 @@ def test_repack_kernel_equals_the_indexing_expression(blocks, ncols, src_c0, dst
 # ----------------------------------------------------------------------------------------------------------------------
 # d. the modules on split spheres against the fp64 restatement
 # ----------------------------------------------------------------------------------------------------------------------
-def _start(rank, world, port):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.setdefault("TORCHDYNAMO_DISABLE", "1")
-    from _fullsize import share_gpu
-    share_gpu(rank, world)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-
-
 def _global_rel(a, b):
     """rel-L2 of the gathered result: the ranks' shards of ``a`` against their shards of the reference ``b``"""
     a = a.detach().cpu()
@@ -152,10 +134,8 @@ GRIDS = [(33, 64, 33, 33, "equiangular", 3),          # poles on the grid, odd p
          (31, 64, 30, 24, "lobatto", 35)]             # ragged latitudes, truncated orders, more than one 32-column block
 
 
-def _worker_modules(rank, world, port, h, w, bf16):
-    _start(rank, world, port)
-    was = torch.backends.cuda.matmul.allow_tf32
-    try:
+def _worker_modules(rank, world, rendezvous, h, w, bf16):
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -213,24 +193,18 @@ def _worker_modules(rank, world, port, h, w, bf16):
                 if rank == 0:
                     print(f"h{h}w{w} {nlat}x{nlon} P={P} bf16 input: fwd {eb:.2e}", flush=True)
                 assert yb.dtype == torch.complex64 and eb <= TOL, (rank, eb)
-        dist.barrier()
-    finally:
-        torch.backends.cuda.matmul.allow_tf32 = was
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,bf16", [(2, 2, True), (1, 2, False), (3, 1, False)])
 def test_distributed_vector_modules_match_fp64(h, w, bf16):
-    mp.spawn(_worker_modules, args=(h * w, _free_port(), h, w, bf16), nprocs=h * w, join=True)
+    launch(_worker_modules, h * w, h, w, bf16, limit=240)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # e. the two losses on split groups against the fixtures recorded from the reference's own classes
 # ----------------------------------------------------------------------------------------------------------------------
-def _worker_losses(rank, world, port, h, w, n):
-    _start(rank, world, port)
-    was = torch.backends.cuda.matmul.allow_tf32
-    try:
+def _worker_losses(rank, world, rendezvous, h, w, n):
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -267,10 +241,6 @@ def _worker_losses(rank, world, port, h, w, n):
                 print(f"h{h}w{w} x ensemble {n} {case}{' (spatial weights)' if wgt is not None else ''}: value {ev:.2e} gradient {eg:.2e}", flush=True)
             assert ev <= 1e-5 and eg <= 1e-5, (rank, case, ev, eg)
         assert ran >= 2
-        dist.barrier()
-    finally:
-        torch.backends.cuda.matmul.allow_tf32 = was
-        dist.destroy_process_group()
 
 
 @pytest.mark.parametrize("h,w,n", [(2, 2, 1), (2, 1, 2)])
@@ -278,15 +248,14 @@ def test_losses_on_split_groups_match_the_reference_fixtures(h, w, n):
     """every recorded case scattered over h2 w2, and the cases with an even member count over h2 w1 x ensemble 2: loss value and
     gathered forecast gradient within 1e-5, the gate of test_losses_match_the_reference_fixtures (same fixtures)"""
     assert os.path.exists(GOLDEN)
-    mp.spawn(_worker_losses, args=(h * w * n, _free_port(), h, w, n), nprocs=h * w * n, join=True)
+    launch(_worker_losses, h * w * n, h, w, n, limit=240)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
 # f. graph replay of the exchange path with groups of one rank
 # ----------------------------------------------------------------------------------------------------------------------
-def _worker_graph(rank, world, port):
-    _start(rank, world, port)
-    try:
+def _worker_graph(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous):
         import makani_amd as ma
         import makani_amd.distributed as thd
         dev = torch.device("cuda:0")
@@ -317,9 +286,7 @@ def _worker_graph(rank, world, port):
         graph.replay()
         torch.cuda.synchronize()
         assert torch.equal(out, eager)
-    finally:
-        dist.destroy_process_group()
 
 
 def test_exchange_path_replays_from_a_captured_graph():
-    mp.spawn(_worker_graph, args=(1, _free_port()), nprocs=1, join=True)
+    launch(_worker_graph, 1, limit=240)

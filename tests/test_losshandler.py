@@ -9,6 +9,7 @@ import json
 import pytest
 import torch
 
+from _ranks import launch, ranks
 from conftest import load_golden, rel_l2
 
 import _losshandler_ref as ref
@@ -194,12 +195,8 @@ def test_a_loss_asked_directly_answers_as_before():
 
 
 # ---- the running statistics over the "batch" group: two CPU ranks over gloo (the update is plain torch) ------------------------
-def _batch_worker(rank, world, port):
-    import os
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+def _batch_worker(rank, world, rendezvous):
+    with ranks(rank, world, rendezvous):
         import makani_amd.comm as mcomm
         mcomm.init(1, 1)
         assert mcomm.get_size("batch") == world and mcomm.get_rank("batch") == rank
@@ -212,16 +209,8 @@ def _batch_worker(rank, world, port):
             whole.update(rows)
         assert int(h.num_batches_tracked) == 4 * 2 == whole.count
         assert rel_l2(h.running_mean, whole.mean) <= 1e-6 and rel_l2(h.running_var, whole.m2) <= 1e-6
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
         mcomm.reset()
 
 
 def test_running_statistics_are_gathered_over_the_batch_group():
-    import socket
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    mp.spawn(_batch_worker, args=(2, port), nprocs=2, join=True)
+    launch(_batch_worker, 2, limit=240)

@@ -1,9 +1,7 @@
 """Host side of ``makani_amd.rollout_buffer``: the constructor contract of the three buffers, the transform of the constant field,
 the pooling of the states of a process group, and the floor of the fp32 formula on the inputs of the GPU tests."""
 import os
-import socket
 import sys
-import time
 
 import numpy as np
 import pytest
@@ -13,6 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _rollout_ref as R  # noqa: E402
+from _ranks import launch, ranks  # noqa: E402
 
 from makani_amd import rollout_buffer as rb  # noqa: E402
 
@@ -131,12 +130,8 @@ def test_constant_field_coefficients_equal_the_oracle_transform(nlat, nlon, grid
     assert abs(one[0] - np.sqrt(4 * np.pi)) <= 1e-12 and np.abs(one[1:]).max() <= 1e-13
 
 
-def _pool_worker(rank, world, port, out):
-    import datetime
-    import torch.distributed as dist
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=60))
-    try:
+def _pool_worker(rank, world, rendezvous, out):
+    with ranks(rank, world, rendezvous, timeout=60):
         import makani_amd.comm as mcomm
         mcomm.init(1, 1)
         assert mcomm.get_size("batch") == 2 and mcomm.get_size("data") == 2
@@ -160,27 +155,11 @@ def _pool_worker(rank, world, port, out):
             assert mean is buf.running_mean and buf.num_samples_tracked.flatten().tolist() == [4, 14, 0]
         if rank == 0:
             open(out, "w").write("ok")
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
-def test_two_ranks_pool_to_the_statistics_of_all_samples(tmp_path, limit=120.0):
-    import torch.multiprocessing as mp
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
+def test_two_ranks_pool_to_the_statistics_of_all_samples(tmp_path):
     out = str(tmp_path / "ok")
-    ctx = mp.spawn(_pool_worker, args=(2, port, out), nprocs=2, join=False)
-    deadline = time.monotonic() + limit
-    try:
-        while not ctx.join(timeout=max(0.0, min(5.0, deadline - time.monotonic()))):
-            assert time.monotonic() < deadline, f"the ranks did not finish within {limit:.0f} s"
-    finally:
-        for p in ctx.processes:
-            if p.is_alive():
-                p.kill()
-            p.join()
+    launch(_pool_worker, 2, out, limit=120)
     assert os.path.exists(out)
 
 

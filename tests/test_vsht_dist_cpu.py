@@ -5,29 +5,11 @@ Legendre launch of modes 0-3, the column-block repack), the exchanges are the pr
 with the serial fp64 pair of tests/_vsht_ref.py, forward and backward, at the gate of the scalar schedule test (1e-5 absolute,
 relative to the largest reference entry where that exceeds one).  Also the constructor contracts of the two losses on a real
 process-group tree."""
-import os
-import socket
-import sys
-
 import torch
-import torch.distributed as dist
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from _ranks import launch, ranks
+
 GATE = 1e-5
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _teardown():
-    try:
-        dist.barrier()
-    finally:
-        dist.destroy_process_group()
 
 
 def _round32(n):
@@ -128,13 +110,9 @@ def _polar_exchanges(thd):
     return sum(v["all_to_alls"] for k, v in thd.COMM_STATS.items() if k[0] == "polar")
 
 
-def _worker(rank, world, port, h, w, cases):
-    sys.path.insert(0, ROOT)
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+def _worker(rank, world, rendezvous, h, w, cases):
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import _vsht_ref as ref
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -218,9 +196,6 @@ def _worker(rank, world, port, h, w, cases):
             _close(back, bref.detach()[spat], f"{tag} round trip", rank)
             _close(xl.grad, xs.grad[spat], f"{tag} round trip grad", rank)
             assert dp.FALLBACKS == [], "the vector pair has no fused form to fall back from"
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 CASES = [(33, 64, 33, 33, "equiangular", 3),       # poles on the grid, odd pair count
@@ -229,7 +204,7 @@ CASES = [(33, 64, 33, 33, "equiangular", 3),       # poles on the grid, odd pair
 
 
 def _run_layout(h, w):
-    mp.spawn(_worker, args=(h * w, _free_port(), h, w, CASES), nprocs=h * w, join=True)
+    launch(_worker, h * w, h, w, CASES, limit=240)
 
 
 def test_vector_schedule_matches_serial_h2w1():
@@ -263,12 +238,9 @@ def test_new_classes_and_entry_point_are_declared():
 NAMES = ["u500", "v500", "u850", "v850", "t500"]
 
 
-def _worker_losses(rank, world, port, h, w, n):
-    sys.path.insert(0, ROOT)
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+def _worker_losses(rank, world, rendezvous, h, w, n):
     torch.set_num_threads(1)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
+    with ranks(rank, world, rendezvous) as dist:
         import makani_amd as ma
         import makani_amd.comm as mcomm
         import makani_amd.distributed as thd
@@ -288,10 +260,7 @@ def _worker_losses(rank, world, port, h, w, n):
             off = cls(**kw)                                                              # flags off: the serial modules on any tree
             assert not off.spatial_distributed and not off.ensemble_distributed and not isinstance(off.__dict__["_modules"][
                 "ivsht" if cls is ma.GradientCRPSLoss else "isht"], thd.DistributedInverseRealVectorSHT)
-        dist.barrier()
-    finally:
-        _teardown()
 
 
 def test_losses_construct_with_both_flags_on_a_real_tree():
-    mp.spawn(_worker_losses, args=(4, _free_port(), 2, 1, 2), nprocs=4, join=True)
+    launch(_worker_losses, 4, 2, 1, 2, limit=240)
