@@ -381,8 +381,8 @@ __global__ __launch_bounds__(NT, WGS) void conv_nn_kernel(const ConvNN p, int ti
             };
             if (p.act) {
                 if (p.Ypre) put(p.Ypre, v);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = gelu_f(v[e]);
+                // the forward GELU of every bf16 kernel (common.h): x (1 + erf) / 2 has no digit left below x = -4
+                gelu_fast_n<8>(v);
             }
             if (p.G) {
                 float g[8];
@@ -2043,62 +2043,7 @@ extern "C" int mk_conv1x1_nn_rnorm(const void* A, const void* X, void* Y, void* 
     return mk_check_launch("mk_conv1x1_nn_rnorm");
 }
 
-// ---- host-side plan of the weight gradient -------------------------------------------------
-namespace {
-struct WgPlan {
-    bool ring;          // ring kernel (big tiles) or the 128 x 128 tile kernel
-    bool swap;          // ring: P = X, Q = G
-    int tp;             // ring: slab height (256 / 192)
-    int slabs;
-    int qslabs;         // ring: 384-row slabs of Q
-    long long S;        // pixel splits (all batch entries)
-    long long chunk;    // pixels per split
-};
-
-WgPlan wgrad_plan(int M, int K, int B, long long N) {
-    WgPlan pl{};
-    const int big = M > K ? M : K, small = M > K ? K : M;
-    // ring kernel: the smaller channel count fits one 384-row tile, the other one is cut into slabs; 32-bit byte
-    // offsets inside one batch entry; at least a few pixel tiles per split
-    if (big >= 96 && N * 2 * 384 < (1ll << 31) && N >= 2048) {
-        pl.ring = true;
-        int q, pr;                                   // rows of Q (384-row slabs; one slab = held in full) and of P (slabs of tp)
-        if (big <= 384) { q = big; pr = small; }
-        else if (small <= 384) { q = small; pr = big; }
-        else { q = big; pr = small; }                // both large (FourCastNet3): the longer operand in 384-row slabs
-        // Q = X (k) unless that puts the larger operand in P's place the wrong way round
-        const bool q_is_x = (K == q) && !(M == q && M > K);
-        pl.swap = !q_is_x;
-        pl.tp = (pr > 192 && pr % 256 != 192 && (pr % 192 != 0 || pr % 256 == 0)) ? 256 : 192;
-        if (pr <= 192) pl.tp = 192;
-        pl.slabs = (pr + pl.tp - 1) / pl.tp;
-        pl.qslabs = (q + 383) / 384;
-        long long per_b = 256 / ((long long)pl.slabs * pl.qslabs * B);
-        if (per_b < 1) per_b = 1;
-        // at least 512 pixels (8 tiles of 64) per split.  1024 left most of the chip idle on shard-sized grids (14 400 pixels per rank
-        // at h4 w2: 45 workgroups); 512: -20 ... -25 % per launch there, +-1 % at 115 200 pixels and above, 256 / 128 no better
-        // (profiles/r05_ab_wgrad_shard_minpx.txt)
-        const long long maxs = (N + 511) / 512;
-        if (per_b > maxs) per_b = maxs;
-        long long chunk = ((N + per_b - 1) / per_b + 63) / 64 * 64;
-        per_b = (N + chunk - 1) / chunk;             // no empty splits
-        pl.chunk = chunk;
-        pl.S = per_b * B;
-        return pl;
-    }
-    const int tiles = ((M + 127) / 128) * ((K + 127) / 128);
-    long long per_b = 1024 / ((long long)tiles * B);
-    if (per_b < 1) per_b = 1;
-    const long long maxs = (N + 2047) / 2048;        // at least 2048 pixels per split
-    if (per_b > maxs) per_b = maxs;
-    long long chunk = (N + per_b - 1) / per_b;
-    chunk = (chunk + 127) / 128 * 128;
-    pl.chunk = chunk;
-    pl.S = per_b * B;
-    return pl;
-}
-}  // namespace
-
+// ---- weight gradient: WgPlan / wgrad_plan, the host-side plan, live in conv1x1_plan.h ----------
 extern "C" long long mk_conv1x1_wgrad_workspace(int M, int K, int B, long long N) {
     // number of fp32 elements the caller must provide as `part` (the (S, M, K) partial products, then (S, M) partial row sums
     // of G for mk_conv1x1_wgrad_bias)

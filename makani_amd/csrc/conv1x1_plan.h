@@ -1,5 +1,6 @@
 // Which kernel mk_conv1x1_nn launches for a shape.  Plain C++ without HIP, so that the CPU suite can compile this file on its
-// own and check the table of the networks' shapes (tests/test_host_logic.py).
+// own and check the table of the networks' shapes (tests/test_host_logic.py).  Below it the plan of the weight gradient
+// (wgrad_plan), which tests/test_conv_exact_cases.py checks the exact-data case tables against.
 #pragma once
 
 enum class ConvNnKernel {
@@ -48,4 +49,58 @@ inline int conv_nn_ring_rows(int M, int K, int B, long long N, bool has_epilogue
     const long long tiles384 = ((N + 255) / 256) * B;
     if (rows == 192 && M > 192 && M <= 384 && K >= 512 && !has_epilogue && tiles384 >= 256 && ring384_env != 0) return 384;
     return rows;
+}
+
+// ---- host-side plan of the weight gradient (mk_conv1x1_wgrad, mk_conv1x1_wgrad_bias) ----------
+struct WgPlan {
+    bool ring;          // ring kernel (big tiles) or the 128 x 128 tile kernel
+    bool swap;          // ring: P = X, Q = G
+    int tp;             // ring: slab height (256 / 192)
+    int slabs;
+    int qslabs;         // ring: 384-row slabs of Q
+    long long S;        // pixel splits (all batch entries)
+    long long chunk;    // pixels per split
+};
+
+inline WgPlan wgrad_plan(int M, int K, int B, long long N) {
+    WgPlan pl{};
+    const int big = M > K ? M : K, small = M > K ? K : M;
+    // ring kernel: the smaller channel count fits one 384-row tile, the other one is cut into slabs; 32-bit byte
+    // offsets inside one batch entry; at least a few pixel tiles per split
+    if (big >= 96 && N * 2 * 384 < (1ll << 31) && N >= 2048) {
+        pl.ring = true;
+        int q, pr;                                   // rows of Q (384-row slabs; one slab = held in full) and of P (slabs of tp)
+        if (big <= 384) { q = big; pr = small; }
+        else if (small <= 384) { q = small; pr = big; }
+        else { q = big; pr = small; }                // both large (FourCastNet3): the longer operand in 384-row slabs
+        // Q = X (k) unless that puts the larger operand in P's place the wrong way round
+        const bool q_is_x = (K == q) && !(M == q && M > K);
+        pl.swap = !q_is_x;
+        pl.tp = (pr > 192 && pr % 256 != 192 && (pr % 192 != 0 || pr % 256 == 0)) ? 256 : 192;
+        if (pr <= 192) pl.tp = 192;
+        pl.slabs = (pr + pl.tp - 1) / pl.tp;
+        pl.qslabs = (q + 383) / 384;
+        long long per_b = 256 / ((long long)pl.slabs * pl.qslabs * B);
+        if (per_b < 1) per_b = 1;
+        // at least 512 pixels (8 tiles of 64) per split.  1024 left most of the chip idle on shard-sized grids (14 400 pixels per rank
+        // at h4 w2: 45 workgroups); 512: -20 ... -25 % per launch there, +-1 % at 115 200 pixels and above, 256 / 128 no better
+        // (profiles/r05_ab_wgrad_shard_minpx.txt)
+        const long long maxs = (N + 511) / 512;
+        if (per_b > maxs) per_b = maxs;
+        long long chunk = ((N + per_b - 1) / per_b + 63) / 64 * 64;
+        per_b = (N + chunk - 1) / chunk;             // no empty splits
+        pl.chunk = chunk;
+        pl.S = per_b * B;
+        return pl;
+    }
+    const int tiles = ((M + 127) / 128) * ((K + 127) / 128);
+    long long per_b = 1024 / ((long long)tiles * B);
+    if (per_b < 1) per_b = 1;
+    const long long maxs = (N + 2047) / 2048;        // at least 2048 pixels per split
+    if (per_b > maxs) per_b = maxs;
+    long long chunk = (N + per_b - 1) / per_b;
+    chunk = (chunk + 127) / 128 * 128;
+    pl.chunk = chunk;
+    pl.S = per_b * B;
+    return pl;
 }
