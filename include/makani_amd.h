@@ -850,6 +850,67 @@ int mk_loss_prep_fwd(const void* prd, const void* tar, const void* inp, long lon
 int mk_loss_prep_bwd(const void* g_prd_t, const void* g_mean, const void* g_mean_t, void* g_prd, int dtype, float inv, int B, int E,
                      long long n, void* stream);
 
+/* ---- imputation of missing inputs and the output tail of FourCastNet3.1 (csrc/impute.hip; makani/models/common/imputation.py,
+ *      makani/models/networks/fourcastnet3_1.py:1062-1080,1127-1131) -------------------------------------------------------------
+ * Pointwise in space: one thread per pixel, or per four consecutive pixels when HW (and the mask strides) are multiples of 4 and
+ * every tensor pointer is 16-byte aligned.  x, y, g, gx, d, xin are f32 | bf16 of ONE dtype, contiguous (B, C, HW); the arithmetic is
+ * fp32, rounded once.  Nothing is read on the host and there are no atomics: the launches can be captured in a graph and repeats
+ * are bit-identical.
+ *
+ * MLPImputation, x (B, C, HW) -> y (B, C, HW), NI <= MK_IMPUTE_SLOTS imputed channels imp_ch, C <= MK_IMPUTE_CHANNELS, hidden <=
+ * MK_IMPUTE_HIDDEN (beyond: MK_EUNSUP):
+ *     m_j = isnan(x[imp_ch[j]]) | (mask operand != 0);   xc = x with 0 at the masked entries of the imputed channels
+ *     h_k = b1_k + sum_c W1[k][c] xc_c;   a_k = act(h_k);   o_j = sum_k W2[j][k] a_k;   y[imp_ch[j]] = m_j ? o_j : x[imp_ch[j]]
+ * and every other entry of y is a copy of x.  act: MK_IMPUTE_ACT_GELU (exact erf), _RELU, _SILU, _SIN.  The mask operand by
+ * mask_kind: MK_IMPUTE_MASK_NONE; _BOOL (one byte per element), _F32, _BF16: `mask` with Nm = 1 | NI planes of HW elements per
+ * sample, sample b at element b m_sb (0: one mask for all samples); _CHANNEL: channel mask_ch of x itself (`mask` is ignored).
+ * The DEVICE table tab (MK_IMPUTE_TAB 32-bit words): W1 TRANSPOSED (MK_IMPUTE_CHANNELS, MK_IMPUTE_HIDDEN) f32, b1 (MK_IMPUTE_HIDDEN),
+ * W2 (MK_IMPUTE_SLOTS, MK_IMPUTE_HIDDEN), all zero beyond C, hidden, NI; then int32: imp_ch (MK_IMPUTE_SLOTS; beyond NI a VALID
+ * channel: it is read, the value is dropped), slot (MK_IMPUTE_CHANNELS: j for imp_ch[j], -1 otherwise).  The channel indices are
+ * NOT checked (device memory): the caller guarantees that they are < C and pairwise distinct.
+ *   mk_impute_mlp_bwd: from g (B, C, HW), the saved x and the mask operand (h is recomputed):  gx_c = g_c + sum_k W1[k][c] gh_k, exactly
+ *       0 at the masked entries of the imputed channels;  gW1 (hidden, C), gb1 (hidden), gW2 (NI, hidden) f32, the sums over samples
+ *       and pixels: one partial sum per block in ws (mk_impute_mlp_workspace floats), added in block order by a second, tiny launch.
+ *
+ * ConstantImputation, w (C) f32: y = (mask | isnan(x)) ? w_c : x, the mask (kinds NONE, BOOL, F32, BF16) addressed as
+ * mask + b m_sb + c m_sc + p (a stride of 0 broadcasts).  mk_impute_const_bwd: gx = masked ? 0 : g, gw (C) f32 = the sum of g over the
+ * masked entries: partial sums in ws (B C mk_impute_chunks(HW) floats), added in index order.
+ *
+ * The output tail, d (B, Co, HW) the decoder's output, xin (B, Cin, HW) the network's input:
+ *     y_c = clamp_c(d_c + [pred_ch != NULL] xin[pred_ch[c]]),   clamp_c(v) = water[c] ? soft_clamp(v + off_c) - off_c : v,
+ *     soft_clamp(t) = 0 (t <= 0), t^2 (t < 1/2), t - 1/4 (otherwise)
+ * pred_ch (Co) int32 DEVICE or NULL (no skip), water (Co) int32 DEVICE flags, off (Co) f32 DEVICE or NULL (= 0).
+ *   mk_fcn31_tail_bwd: gd (B, Co, HW) = g clamp'(.), recomputed from d (and xin); with the skip also gxin (B, Cin, HW): gd on the
+ *       channels pred_ch (pairwise distinct), ZERO on the Cin - Co others, listed in rest (int32 DEVICE): every element is written once. */
+#define MK_IMPUTE_CHANNELS 256
+#define MK_IMPUTE_SLOTS 8
+#define MK_IMPUTE_HIDDEN 32
+#define MK_IMPUTE_TAB (MK_IMPUTE_CHANNELS * MK_IMPUTE_HIDDEN + MK_IMPUTE_HIDDEN + MK_IMPUTE_SLOTS * MK_IMPUTE_HIDDEN + MK_IMPUTE_SLOTS + MK_IMPUTE_CHANNELS)
+#define MK_IMPUTE_MASK_NONE 0
+#define MK_IMPUTE_MASK_BOOL 1
+#define MK_IMPUTE_MASK_F32 2
+#define MK_IMPUTE_MASK_BF16 3
+#define MK_IMPUTE_MASK_CHANNEL 4
+#define MK_IMPUTE_ACT_GELU 0
+#define MK_IMPUTE_ACT_RELU 1
+#define MK_IMPUTE_ACT_SILU 2
+#define MK_IMPUTE_ACT_SIN 3
+int mk_impute_mlp_fwd(const void* x, void* y, int dtype, const float* tab, const void* mask, int mask_kind, int Nm, long long m_sb,
+                      int mask_ch, int act, int B, int C, int NI, int hidden, long long HW, void* stream);
+long long mk_impute_mlp_workspace(int B, int C, int NI, int hidden, long long HW);
+int mk_impute_mlp_bwd(const void* g, const void* x, void* gx, float* gW1, float* gb1, float* gW2, float* ws, int dtype, const float* tab,
+                      const void* mask, int mask_kind, int Nm, long long m_sb, int mask_ch, int act, int B, int C, int NI, int hidden,
+                      long long HW, void* stream);
+int mk_impute_chunks(long long HW);
+int mk_impute_const_fwd(const void* x, void* y, int dtype, const float* w, const void* mask, int mask_kind, long long m_sb, long long m_sc,
+                        int B, int C, long long HW, void* stream);
+int mk_impute_const_bwd(const void* g, const void* x, void* gx, float* gw, float* ws, int dtype, const void* mask, int mask_kind,
+                        long long m_sb, long long m_sc, int B, int C, long long HW, void* stream);
+int mk_fcn31_tail_fwd(const void* d, const void* xin, void* y, int dtype, const int* pred_ch, const int* water, const float* off, int B,
+                      int Co, int Cin, long long HW, void* stream);
+int mk_fcn31_tail_bwd(const void* g, const void* d, const void* xin, void* gd, void* gxin, int dtype, const int* pred_ch, const int* water,
+                      const float* off, const int* rest, int B, int Co, int Cin, long long HW, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,8 @@ from .rollout_buffer import MeanStdBuffer, TemporalAverageBuffer, SpectrumAverag
 from .constraints import (ConstraintsWrapper, HydrostaticBalanceProjection, NonNegativeConstraint, constrain_model_handle,
                           get_matching_channels_pl)
 from .interpolant import InterpolationWrapper, TimeAwareInterpolationWrapper, StochasticInterpolantWrapper
+from .imputation import MLPImputation, ConstantImputation
+from .fcn31 import AtmoSphericNeuralOperatorNet31, LearnablePositionEmbedding
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DistributedRealVectorSHT", "DistributedInverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
@@ -40,4 +42,5 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "MeanStdBuffer", "TemporalAverageBuffer", "SpectrumAverageBuffer", "ZonalSpectrumAverageBuffer", "power_spectrum",
            "ConstraintsWrapper", "HydrostaticBalanceProjection", "NonNegativeConstraint", "constrain_model_handle",
            "get_matching_channels_pl",
-           "InterpolationWrapper", "TimeAwareInterpolationWrapper", "StochasticInterpolantWrapper"]
+           "InterpolationWrapper", "TimeAwareInterpolationWrapper", "StochasticInterpolantWrapper",
+           "MLPImputation", "ConstantImputation", "AtmoSphericNeuralOperatorNet31", "LearnablePositionEmbedding"]

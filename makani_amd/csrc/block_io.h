@@ -72,6 +72,27 @@ __device__ __forceinline__ float mk_block_sum_t0(float v, float* red) {
     return t;
 }
 
+// N sums at once behind ONE barrier, each in the order above; the totals are returned to THREAD 0 in place (the other threads
+// keep partial values).  red holds one row of NT / 64 floats per sum; as with mk_block_sum_t0 there is no barrier in front of
+// the writes, so a caller that sums repeatedly alternates between two such blocks of rows (impute.hip).
+template <int NT, int N>
+__device__ __forceinline__ void mk_block_sums_t0(float (&v)[N], float (*red)[NT / 64]) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+        if ((threadIdx.x & 63) == 0) red[k][threadIdx.x >> 6] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            float t = 0.f;
+            for (int i = 0; i < NT / 64; ++i) t += red[k][i];
+            v[k] = t;
+        }
+    }
+}
+
 // The total is returned to EVERY thread; two barriers.  The one in front of the write to red waits for the readers of the
 // previous sum, so consecutive sums of a block may share one red.
 template <int NT>

@@ -2057,6 +2057,225 @@ class HydroSumsFn(torch.autograd.Function):
         return (gx if gx.dtype == dtype_in else gx.to(dtype_in)), None, None, None, None
 
 
+# ---- imputation of missing inputs and the output tail of FourCastNet3.1 (csrc/impute.hip) ---------------------------------------
+IMPUTE_CHANNELS, IMPUTE_SLOTS, IMPUTE_HIDDEN, IMPUTE_TAB = (_lib.CONSTS["MK_IMPUTE_" + k] for k in ("CHANNELS", "SLOTS", "HIDDEN", "TAB"))
+MASK_NONE, MASK_BOOL, MASK_F32, MASK_BF16, MASK_CHANNEL = (_lib.CONSTS["MK_IMPUTE_MASK_" + k] for k in ("NONE", "BOOL", "F32", "BF16", "CHANNEL"))
+IMPUTE_ACTS = {k.lower(): _lib.CONSTS["MK_IMPUTE_ACT_" + k] for k in ("GELU", "RELU", "SILU", "SIN")}
+
+
+def impute_check(C_, NI, hidden):
+    """the capacities of ``mk_impute_mlp_fwd`` (the hidden column and the imputed channels of a pixel live in registers)"""
+    if not (1 <= C_ <= IMPUTE_CHANNELS and 1 <= NI <= IMPUTE_SLOTS and 1 <= hidden <= IMPUTE_HIDDEN):
+        raise NotImplementedError(f"MLPImputation with {C_} channels, {NI} imputed channels and {hidden} hidden units: the HIP kernel holds "
+                                  f"at most {IMPUTE_CHANNELS} channels, {IMPUTE_SLOTS} imputed channels and {IMPUTE_HIDDEN} hidden units")
+
+
+def impute_itab(imp_ch, C_, device):
+    """the int32 tail of the table of ``mk_impute_mlp_fwd``: imp_ch padded with a valid channel, then the channel -> slot map.  The
+    channel list is checked here (the kernels do not check it)."""
+    imp_ch = [int(c) for c in imp_ch]
+    if not imp_ch or len(set(imp_ch)) != len(imp_ch) or min(imp_ch) < 0 or max(imp_ch) >= C_:
+        raise ValueError(f"the imputed channels {imp_ch} must be distinct channels of the {C_} input channels")
+    slot = [-1] * IMPUTE_CHANNELS
+    for j, c in enumerate(imp_ch):
+        slot[c] = j
+    return torch.tensor(imp_ch + [imp_ch[0]] * (IMPUTE_SLOTS - len(imp_ch)) + slot, dtype=torch.int32, device=device)
+
+
+def impute_table(w1, b1, w2, itab):
+    """the device table of ``mk_impute_mlp_fwd`` from W1 (hidden, C), b1 (hidden), W2 (NI, hidden); device work only"""
+    hidden, C_ = w1.shape
+    f = torch.zeros((IMPUTE_CHANNELS + 1 + IMPUTE_SLOTS, IMPUTE_HIDDEN), dtype=torch.float32, device=w1.device)
+    f[:C_, :hidden] = w1.detach().t()
+    f[IMPUTE_CHANNELS, :hidden] = b1.detach()
+    f[IMPUTE_CHANNELS + 1:IMPUTE_CHANNELS + 1 + w2.shape[0], :hidden] = w2.detach()
+    return torch.cat([f.reshape(-1), itab.view(torch.float32)])
+
+
+def _impute_mask(mask, lead, planes, H, W):
+    """a mask that broadcasts to (*lead, planes, H, W) as (tensor | None, kind, its planes (1 | planes), sample stride, plane stride)"""
+    if mask is None:
+        return None, MASK_NONE, 1, 0, 0
+    m = mask if mask.dtype in (torch.bool, torch.float32, torch.bfloat16) else mask != 0
+    nd = len(lead) + 3
+    if m.dim() > nd:
+        raise ValueError(f"the mask {tuple(mask.shape)} has more dimensions than the input")
+    m = m.reshape((1,) * (nd - m.dim()) + tuple(m.shape))
+    Nm = m.shape[-3]
+    if Nm not in (1, planes) or any(a not in (1, b) for a, b in zip(m.shape[:-3], lead)) or m.shape[-2] not in (1, H) or m.shape[-1] not in (1, W):
+        raise ValueError(f"the mask {tuple(mask.shape)} does not broadcast to {(*lead, planes, H, W)}")
+    one = all(s == 1 for s in m.shape[:-3])
+    m = m.expand(*((1,) * len(lead) if one else lead), Nm, H, W).contiguous()
+    kind = MASK_BOOL if m.dtype == torch.bool else (MASK_F32 if m.dtype == torch.float32 else MASK_BF16)
+    return m, kind, Nm, (0 if one else Nm * H * W), (H * W if Nm > 1 else 0)
+
+
+def _back(t, dtype):
+    return t if t.dtype == dtype else t.to(dtype)
+
+
+class ImputeMlpFn(torch.autograd.Function):
+    """``mk_impute_mlp_fwd`` / ``mk_impute_mlp_bwd``: x (..., C, H, W) f32 | bf16, W1 (hidden, C), b1 (hidden), W2 (NI, hidden).  The
+    mask is a tensor, or ``mask_channel`` names the channel of x that holds it.  ``tab`` is ``impute_table`` of the same weights (the
+    module caches it per parameter version); w1, b1, w2 themselves only receive the gradients.  Saved: x, the mask and the table."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, tab, mask, mask_channel, act):
+        dtype_in = x.dtype
+        x = _planes(x, "imputation")
+        lead, (C_, H, W) = tuple(x.shape[:-3]), x.shape[-3:]
+        (hidden, Cw), NI = w1.shape, w2.shape[0]
+        if Cw != C_:
+            raise RuntimeError(f"the imputation expects {Cw} channels, got {C_}")
+        impute_check(C_, NI, hidden)
+        if tab.device != x.device or tab.numel() != IMPUTE_TAB:
+            raise RuntimeError("the imputation's table lives on another device than its input, or is not a table of impute_table")
+        B, hw = (int(np.prod(lead)) if lead else 1), H * W
+        if mask_channel is not None:
+            if mask is not None:
+                raise ValueError("give either a mask or the channel of x that holds it, not both")
+            if not 0 <= mask_channel < C_:
+                raise ValueError(f"mask channel {mask_channel} outside the {C_} input channels")
+            m, kind, Nm, m_sb, mch = None, MASK_CHANNEL, 1, 0, int(mask_channel)
+        else:
+            m, kind, Nm, m_sb, _ = _impute_mask(mask, lead, NI, H, W)
+            mch = 0
+        y = torch.empty_like(x)
+        margs = (ptr(m), kind, Nm, m_sb, mch, act, B, C_, NI, hidden, hw)
+        check(lib().mk_impute_mlp_fwd(ptr(x), ptr(y), dtype_code(x), ptr(tab), *margs, stream()), "mk_impute_mlp_fwd")
+        ctx.save_for_backward(x, tab, m)
+        ctx.meta = (margs[1:], dtype_in, tuple(w1.shape), tuple(b1.shape), tuple(w2.shape), (w1.dtype, b1.dtype, w2.dtype))
+        return _back(y, dtype_in) if dtype_in in (torch.float16, torch.float64) else y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, tab, m = ctx.saved_tensors
+        margs, dtype_in, s1, sb, s2, wdt = ctx.meta
+        B, C_, NI, hidden, hw = margs[-5:]
+        g = g.to(x.dtype).contiguous()
+        gx = torch.empty_like(x)
+        new = lambda *s: torch.empty(s, dtype=torch.float32, device=x.device)          # noqa: E731
+        gw1, gb1, gw2 = new(hidden, C_), new(hidden), new(NI, hidden)
+        ws = new(lib().mk_impute_mlp_workspace(B, C_, NI, hidden, hw))
+        check(lib().mk_impute_mlp_bwd(ptr(g), ptr(x), ptr(gx), ptr(gw1), ptr(gb1), ptr(gw2), ptr(ws), dtype_code(x), ptr(tab), ptr(m), *margs,
+                                      stream()), "mk_impute_mlp_bwd")
+        return (_back(gx, dtype_in), _back(gw1.reshape(s1), wdt[0]), _back(gb1.reshape(sb), wdt[1]), _back(gw2.reshape(s2), wdt[2]),
+                None, None, None, None)
+
+
+class ImputeConstFn(torch.autograd.Function):
+    """``mk_impute_const_fwd`` / ``mk_impute_const_bwd``: x (..., C, H, W) f32 | bf16, weight (C, 1, 1), a mask broadcastable to x"""
+
+    @staticmethod
+    def forward(ctx, x, weight, mask):
+        dtype_in = x.dtype
+        x = _planes(x, "imputation")
+        lead, (C_, H, W) = tuple(x.shape[:-3]), x.shape[-3:]
+        if weight.numel() != C_:
+            raise RuntimeError(f"the imputation expects {weight.numel()} channels, got {C_}")
+        B, hw = (int(np.prod(lead)) if lead else 1), H * W
+        if B > 65535 or C_ > 65535:
+            raise NotImplementedError(f"ConstantImputation over {B} samples of {C_} channels: at most 65535 each (one grid row each)")
+        m, kind, _, m_sb, m_sc = _impute_mask(mask, lead, C_, H, W)
+        w = weight.detach().reshape(-1).float().contiguous()
+        y = torch.empty_like(x)
+        margs = (ptr(m), kind, m_sb, m_sc, B, C_, hw)
+        check(lib().mk_impute_const_fwd(ptr(x), ptr(y), dtype_code(x), ptr(w), *margs, stream()), "mk_impute_const_fwd")
+        ctx.save_for_backward(x, m)
+        ctx.meta = (margs[1:], dtype_in, tuple(weight.shape), weight.dtype)
+        return _back(y, dtype_in) if dtype_in in (torch.float16, torch.float64) else y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, m = ctx.saved_tensors
+        margs, dtype_in, ws_, wdt = ctx.meta
+        B, C_, hw = margs[-3:]
+        g = g.to(x.dtype).contiguous()
+        gx = torch.empty_like(x)
+        gw = torch.empty((C_,), dtype=torch.float32, device=x.device)
+        ws = torch.empty((B * C_ * lib().mk_impute_chunks(hw),), dtype=torch.float32, device=x.device)
+        check(lib().mk_impute_const_bwd(ptr(g), ptr(x), ptr(gx), ptr(gw), ptr(ws), dtype_code(x), ptr(m), *margs, stream()),
+              "mk_impute_const_bwd")
+        return _back(gx, dtype_in), _back(gw.reshape(ws_), wdt), None
+
+
+@dataclass
+class TailTable:
+    """The descriptor of ``mk_fcn31_tail_fwd`` / ``mk_fcn31_tail_bwd``: device int32 lists and the f32 offsets (or None)"""
+    pred: torch.Tensor
+    water: torch.Tensor
+    off: torch.Tensor
+    rest: torch.Tensor
+    Co: int
+    Cin: int
+
+
+def tail_table(Co, water_channels, offsets, pred_channels, Cin, device) -> TailTable:
+    """``water_channels`` index the OUTPUT, ``offsets`` (one per water channel) or None, ``pred_channels`` (Co, distinct, into the
+    Cin input channels) or None without the skip.  The lists are checked here (the kernels do not check them)."""
+    water_channels = [int(c) for c in water_channels]
+    if len(set(water_channels)) != len(water_channels) or any(not 0 <= c < Co for c in water_channels):
+        raise ValueError(f"the water channels {water_channels} must be distinct channels of the {Co} output channels")
+    water = torch.zeros(Co, dtype=torch.int32)
+    if water_channels:
+        water[water_channels] = 1
+    off = None
+    if offsets is not None and water_channels:
+        off = torch.zeros(Co, dtype=torch.float32)
+        off[water_channels] = offsets.detach().reshape(-1).to(device="cpu", dtype=torch.float32)
+        off = off.to(device)
+    pred = rest = None
+    if pred_channels is not None:
+        pc = [int(c) for c in pred_channels]
+        if len(pc) != Co or len(set(pc)) != Co or min(pc) < 0 or max(pc) >= Cin:
+            raise ValueError(f"the skip needs {Co} distinct channels of the {Cin} input channels, got {pc}")
+        pred = torch.tensor(pc, dtype=torch.int32, device=device)
+        rest = torch.tensor([c for c in range(Cin) if c not in set(pc)] or [0], dtype=torch.int32, device=device)
+    return TailTable(pred, water.to(device), off, rest, Co, Cin if pred_channels is not None else 0)
+
+
+class Fcn31TailFn(torch.autograd.Function):
+    """``mk_fcn31_tail_fwd`` / ``mk_fcn31_tail_bwd``: d (..., Co, H, W) the decoder's output, xin (..., Cin, H, W) the network's input
+    (None without the skip) -> clamp(d + xin[pred]); the gradients of both, zeros on the input channels the skip does not read"""
+
+    @staticmethod
+    def forward(ctx, d, xin, t):
+        d_in, x_in = d.dtype, (xin.dtype if xin is not None else None)
+        d = _planes(d, "the output tail")
+        if d.shape[-3] != t.Co:
+            raise RuntimeError(f"the output tail expects {t.Co} channels, got {d.shape[-3]}")
+        if t.water.device != d.device:
+            raise RuntimeError("the tail's tables live on another device than its input")
+        skip = t.pred is not None
+        if skip:
+            if xin is None or xin.shape[-3] != t.Cin or xin.shape[:-3] != d.shape[:-3] or xin.shape[-2:] != d.shape[-2:]:
+                raise RuntimeError(f"the skip expects the input (..., {t.Cin}, H, W) next to the decoder's output {tuple(d.shape)}")
+            xin = _planes(xin, "the output tail")
+            if xin.dtype != d.dtype:          # x + residual.to(x.dtype): the decoder's dtype decides (bf16 under autocast)
+                xin = xin.to(d.dtype)
+        else:
+            xin = None
+        hw = d.shape[-2] * d.shape[-1]
+        B = d.numel() // (t.Co * hw)
+        y = torch.empty_like(d)
+        check(lib().mk_fcn31_tail_fwd(ptr(d), ptr(xin), ptr(y), dtype_code(d), ptr(t.pred), ptr(t.water), ptr(t.off), B, t.Co, t.Cin, hw,
+                                      stream()), "mk_fcn31_tail_fwd")
+        ctx.save_for_backward(d, xin)
+        ctx.meta = (t, B, hw, d_in, x_in)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        d, xin = ctx.saved_tensors
+        t, B, hw, d_in, x_in = ctx.meta
+        g = g.to(d.dtype).contiguous()
+        gd = torch.empty_like(d)
+        gxin = torch.empty_like(xin) if xin is not None else None
+        check(lib().mk_fcn31_tail_bwd(ptr(g), ptr(d), ptr(xin), ptr(gd), ptr(gxin), dtype_code(d), ptr(t.pred), ptr(t.water), ptr(t.off),
+                                      ptr(t.rest), B, t.Co, t.Cin, hw, stream()), "mk_fcn31_tail_bwd")
+        return _back(gd, d_in), (_back(gxin, x_in) if gxin is not None else None), None
+
+
 def loss_prep_launch(prd, tar, inp, flags, inv):
     """``mk_loss_prep_fwd``: prd (B, E, C, H, W) f32 | bf16 contiguous, tar (B, C, H, W), inp (B, C, H, W) a view whose samples are
     contiguous (the last step of a flattened history), both in the dtype of prd -> (mean, prd_t, mean_t, tar_t), None where unselected"""

@@ -11,6 +11,10 @@ or, from Python, ``makani_plugin.register("SFNO_mi355x")`` (``model_registry.reg
 FourCastNet3 (``nettype: "FCN3"`` in config/fourcastnet3.yaml) binds the same way:
 
     nettype: "/path/to/repo/makani_plugin.py:AtmoSphericNeuralOperatorNet"       # or  makani_plugin.register_fcn3("FCN3_mi355x")
+
+and FourCastNet3.1 (``nettype: "FCN3.1"``):
+
+    nettype: "/path/to/repo/makani_plugin.py:AtmoSphericNeuralOperatorNet31"     # or  makani_plugin.register_fcn31("FCN3.1_mi355x")
 """
 import os
 import sys
@@ -19,7 +23,7 @@ _ROOT = os.path.dirname(os.path.abspath(__file__))
 if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
-from makani_amd import (AtmoSphericNeuralOperatorNet, ConstraintsWrapper, MultiStepWrapper, SingleStepWrapper,  # noqa: E402,F401
+from makani_amd import (AtmoSphericNeuralOperatorNet, AtmoSphericNeuralOperatorNet31, ConstraintsWrapper, MultiStepWrapper, SingleStepWrapper,  # noqa: E402,F401
                         SphericalFourierNeuralOperatorNet, StochasticInterpolantWrapper)
 
 
@@ -33,3 +37,9 @@ def register_fcn3(name: str = "FCN3_mi355x") -> None:
     """register FourCastNet3 (``AtmoSphericNeuralOperatorNet``) under ``name`` in makani's registry"""
     from makani.models import model_registry
     model_registry.register_model(AtmoSphericNeuralOperatorNet, name)
+
+
+def register_fcn31(name: str = "FCN3.1_mi355x") -> None:
+    """register FourCastNet3.1 (``AtmoSphericNeuralOperatorNet31``) under ``name`` in makani's registry"""
+    from makani.models import model_registry
+    model_registry.register_model(AtmoSphericNeuralOperatorNet31, name)

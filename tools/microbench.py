@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -988,6 +988,101 @@ def mhandler():
                 print(f"mhandler E={E:2d} {str(dt)[6:]} {nh} handles round {rnd}: fused {tf:7.3f} ms {rate(fused_bytes, tf)} ({fused_bytes / 1e9:.2f} GB)"
                       f" | composed {tc:8.3f} ms {rate(comp_bytes, tc)} ({comp_bytes / 1e9:.2f} GB) = {tc / tf:5.1f} x", flush=True)
             del prd, tar, h
+
+
+def fcn31():
+    """The two full-grid stages of FourCastNet3.1 (csrc/impute.hip) at 721 x 1440, B = 1, forward + backward, f32 and bf16: the
+    SST imputation on 150 input channels (one imputed channel, 2 hidden units, the land mask read from a channel of x, about 30 %
+    of the pixels masked) and the output tail on 73 channels (skip from a 76-channel input, soft clamp with offsets on 14 water
+    channels); each beside the reference's composition in plain torch (slice, isnan, where, scatter, two
+    1x1 convolutions, where, scatter; gather, add, gather, clamp, index_copy; backward by autograd) on the same tensors in the
+    same process, the two timed in turn over two rounds, every timing over a window of at least 0.5 s.  Algorithmic bytes: the
+    imputation reads x and writes y, then reads x and g and writes gx (5 tensors); the tail reads d and the 73 skip planes and
+    writes y, then reads g (and d, xin on the water channels) and writes gd and the full input gradient."""
+    import types
+    import torch.nn.functional as F
+    from makani_amd.imputation import MLPImputation
+
+    def compose_mlp(x, imp, mask, w1, b1, w2):
+        idx = torch.as_tensor(imp, device=x.device)
+        x_sub = x[:, idx]
+        m = torch.logical_or(mask, torch.isnan(x_sub))
+        x_zeroed = torch.where(m, torch.zeros_like(x_sub), x_sub)
+        index = idx.view(1, -1, 1, 1).expand_as(x_zeroed)
+        x_clean = x.scatter(1, index, x_zeroed)
+        o = F.conv2d(F.gelu(F.conv2d(x_clean, w1[:, :, None, None], b1)), w2[:, :, None, None])
+        return x_clean.scatter(1, index, torch.where(m, o, x_zeroed))
+
+    def compose_tail(d, xin, pred, water, off):
+        x = d + xin[:, torch.as_tensor(pred, device=d.device)]
+        wi = torch.as_tensor(water, device=d.device)
+        o = off.view(1, -1, 1, 1).to(x.dtype)
+        t = x[:, wi] + o
+        y = torch.where(t > 0.0, t ** 2, 0.0)
+        return x.index_copy(1, wi, (torch.where(t >= 0.5, t - 0.25, y) - o).to(x.dtype))
+
+    ref = types.SimpleNamespace(compose_mlp=compose_mlp, compose_tail=compose_tail)
+    PEAK = 8.0e12
+    H, W, B = 721, 1440, 1
+    N = H * W
+    gen = torch.Generator().manual_seed(1)
+
+    def timed(fn):
+        once = max(timeit(fn, reps=3, warm=2), 1e-3)
+        return timeit(fn, reps=max(5, int(math.ceil(500.0 / once))), warm=1)
+
+    def report(label, dt, nbytes, ours, composed, err):
+        for rnd in range(2):
+            t, tt = timed(ours), timed(composed)
+            print(f"fcn31 {label:10s} {str(dt)[6:]:8s} round {rnd}: forward + backward {t:7.3f} ms = {nbytes / (t * 1e-3) / 1e12:5.2f} TB/s "
+                  f"= {nbytes / (t * 1e-3) / PEAK * 100:5.1f} % of the HBM roof ({nbytes / 1e9:.2f} GB) | torch composition {tt:7.3f} ms = "
+                  f"{tt / t:5.2f} x | max |kernel - torch| {err[0]:.1e} {err[1]:.1e}", flush=True)
+
+    C, SST, LSM = 150, 4, 148
+    mod = MLPImputation(C, torch.tensor([SST]), 2.0, mask_channel=LSM).to(dev)
+    p = [mod.mlp.fwd[0].weight, mod.mlp.fwd[0].bias, mod.mlp.fwd[2].weight]
+    for dt in (torch.float32, torch.bfloat16):
+        x = torch.randn(B, C, H, W, generator=gen)
+        u = torch.rand(B, H, W, generator=gen)
+        x[:, LSM] = torch.where(u < 0.7, torch.zeros(()), (u - 0.7) / 0.3)
+        x[:, SST] = torch.where(x[:, LSM] != 0, torch.full((), float("nan")), x[:, SST])
+        x = x.to(dt).to(dev).requires_grad_(True)
+        g = torch.randn(B, C, H, W, generator=gen).to(dt).to(dev)
+        w = [t.detach().view(t.shape[:2]).to(dt) if t.dim() == 4 else t.detach().to(dt) for t in p]
+        w = [t.requires_grad_(True) for t in w]
+
+        def ours():
+            return torch.autograd.grad(mod(x), [x] + p, g)[0]
+
+        def composed():
+            return torch.autograd.grad(ref.compose_mlp(x, [SST], (x[:, LSM] != 0)[:, None], *w), [x] + w, g)[0]
+
+        err = ((mod(x).detach().float() - ref.compose_mlp(x, [SST], (x[:, LSM] != 0)[:, None], *w).detach().float()).abs().max().item(),
+               (ours().float() - composed().float()).abs().max().item())
+        report("imputation", dt, 5 * C * B * N * x.element_size(), ours, composed, err)
+        del x, g
+
+    Co, Cin = 73, 76
+    water = [7] + list(range(60, 73))
+    pred = list(range(8)) + list(range(11, 76))
+    off = torch.linspace(0.2, 1.5, len(water))
+    table = ops.tail_table(Co, water, off, pred, Cin, dev)
+    for dt in (torch.float32, torch.bfloat16):
+        d = torch.randn(B, Co, H, W, generator=gen).to(dt).to(dev).requires_grad_(True)
+        xin = torch.randn(B, Cin, H, W, generator=gen).to(dt).to(dev).requires_grad_(True)
+        g = torch.randn(B, Co, H, W, generator=gen).to(dt).to(dev)
+        offd = off.to(dev)
+        nbytes = (3 * Co + Co + 2 * len(water) + Co + Cin) * B * N * d.element_size()
+
+        def ours():
+            return torch.autograd.grad(ops.Fcn31TailFn.apply(d, xin, table), [d, xin], g)
+
+        def composed():
+            return torch.autograd.grad(ref.compose_tail(d, xin, pred, water, offd), [d, xin], g)
+
+        err = ((ours()[0].float() - composed()[0].float()).abs().max().item(), (ours()[1].float() - composed()[1].float()).abs().max().item())
+        report("tail", dt, nbytes, ours, composed, err)
+        del d, xin, g
 
 
 if __name__ == "__main__":
