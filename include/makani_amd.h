@@ -911,6 +911,24 @@ int mk_fcn31_tail_fwd(const void* d, const void* xin, void* y, int dtype, const 
 int mk_fcn31_tail_bwd(const void* g, const void* d, const void* xin, void* gd, void* gxin, int dtype, const int* pred_ch, const int* water,
                       const float* off, const int* rest, int B, int Co, int Cin, long long HW, void* stream);
 
+/* ---- cosine of the solar zenith angle (csrc/zenith.hip; makani/third_party/climt/zenith_angle_v2.py: cos_zenith_angle) ----------
+ *   cosz(t, phi, lambda) = sin phi sin dec(t) + cos phi cos dec(t) cos(gmst(t) - ra(t) + lambda)
+ * The time scalars are evaluated in fp64 from the time itself (the reference holds the days since J2000 in fp32); the field is
+ * formed in fp32 from four scalars per time level and the four fp32 grid tables, without a transcendental per pixel.
+ *   mk_zenith_tables: tab (2 H + 2 W) f32 = sin phi (H) | cos phi (H) | cos lambda (W) | sin lambda (W) from lat_deg (H) and
+ *       lon_deg (W), fp64 DEVICE vectors in degrees; every entry from its own angle in fp64, so a slice of the vectors gives the
+ *       slice of the tables bit for bit (the rank of an h x w split passes its own slices).
+ *   mk_cos_zenith: ONE launch for the B T planes.  times: int64 DEVICE, UTC microseconds since 1970-01-01T00:00, (Bt, T) with
+ *       Bt = B or Bt = 1 (one window shared by the batch).  Plane (b, t) is written at out + b sb + t st elements (f32 | bf16 by
+ *       dtype), H rows of W contiguous elements; planes must not overlap.  Nothing else of plane size is read or written, there
+ *       are no atomics, and nothing is read on the host.
+ *   mk_zenith_advance: times[i] += dt_us for i < n, on the device (stream-ordered behind mk_cos_zenith: a captured pair gives
+ *       the next valid time's planes on every replay). */
+int mk_zenith_tables(const double* lat_deg, const double* lon_deg, float* tab, int H, int W, void* stream);
+int mk_cos_zenith(const long long* times, int Bt, const float* tab, void* out, int dtype, int B, int T, int H, int W, long long sb,
+                  long long st, void* stream);
+int mk_zenith_advance(long long* times, int n, long long dt_us, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

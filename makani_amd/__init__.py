@@ -25,6 +25,7 @@ from .constraints import (ConstraintsWrapper, HydrostaticBalanceProjection, NonN
 from .interpolant import InterpolationWrapper, TimeAwareInterpolationWrapper, StochasticInterpolantWrapper
 from .imputation import MLPImputation, ConstantImputation
 from .fcn31 import AtmoSphericNeuralOperatorNet31, LearnablePositionEmbedding
+from .zenith import ZenithFeatures, cos_zenith_angle
 
 __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "DistributedRealVectorSHT", "DistributedInverseRealVectorSHT", "GradientCRPSLoss", "VortDivCRPSLoss", "SpectralConv", "MLP", "EncoderDecoder", "InstanceNorm2d", "PointwiseConv",
@@ -43,4 +44,5 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "ConstraintsWrapper", "HydrostaticBalanceProjection", "NonNegativeConstraint", "constrain_model_handle",
            "get_matching_channels_pl",
            "InterpolationWrapper", "TimeAwareInterpolationWrapper", "StochasticInterpolantWrapper",
-           "MLPImputation", "ConstantImputation", "AtmoSphericNeuralOperatorNet31", "LearnablePositionEmbedding"]
+           "MLPImputation", "ConstantImputation", "AtmoSphericNeuralOperatorNet31", "LearnablePositionEmbedding",
+           "ZenithFeatures", "cos_zenith_angle"]

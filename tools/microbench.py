@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31] [zenith]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -1083,6 +1083,67 @@ def fcn31():
         err = ((ours()[0].float() - composed()[0].float()).abs().max().item(), (ours()[1].float() - composed()[1].float()).abs().max().item())
         report("tail", dt, nbytes, ours, composed, err)
         del d, xin, g
+
+
+def zenith():
+    """the zenith planes of one rollout step at (B, T, H, W) = (1, 2, 721, 1440), f32 and bf16 (mk_cos_zenith; with mk_zenith_advance
+    behind it as a step runs it), beside the host path of the reference — the fp32 numpy expression on the 2-D grids, then the
+    upload, timed on the host clock to the device synchronise — and as a fraction of the HBM roof on the one write of the planes;
+    a fill_ of the same tensor is the write-only yardstick.  Three rounds, everything timed in turn within each."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import numpy as np
+    import _zenith_ref as R
+    PEAK = 8.0e12
+    B, T, H, W = 1, 2, 721, 1440
+    lat, lon = np.linspace(90.0, -90.0, H), np.linspace(0.0, 360.0, W, endpoint=False)
+    t_us = R.times_us()[2] + np.arange(T, dtype=np.int64) * 6 * 3_600_000_000
+    lon_grid, lat_grid = np.meshgrid(lon, lat)
+    lon_rad = np.deg2rad(lon_grid, dtype=np.float32)
+    sin_lat, cos_lat = (f(np.deg2rad(lat_grid, dtype=np.float32)).astype(np.float32) for f in (np.sin, np.cos))
+
+    def host_path():
+        dec, ra, gmst = (v.astype(np.float32).reshape(T, 1, 1) for v in R.time_scalars(t_us))
+        cosz = sin_lat * np.sin(dec) + cos_lat * np.cos(dec) * np.cos(gmst - ra + lon_rad)
+        return torch.as_tensor(cosz.astype(np.float32)).to(dev).reshape(B, T, H, W)
+
+    def host_ms(reps=5):
+        host_path()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            host_path()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / reps * 1e3
+
+    mods = {dt: ma.ZenithFeatures(lat, lon, n_history=T - 1, dtype=dt).to(dev).set_time(torch.from_numpy(t_us).to(dev)) for dt in (torch.float32, torch.bfloat16)}
+    outs = {dt: m(B) for dt, m in mods.items()}
+    err = (outs[torch.float32].double().cpu() - torch.from_numpy(R.cos_zenith(t_us, lat, lon))).abs().max().item()
+    print(f"zenith ({B}, {T}, {H}, {W}): max |f32 - fp64 restatement| = {err:.2e}, |host path - fp64| = "
+          f"{(host_path().double().cpu() - torch.from_numpy(R.cos_zenith(t_us, lat, lon))).abs().max().item():.2e}", flush=True)
+    # device time without the host's enqueue cost (two ctypes calls: about 25 us): NG launches each in a captured graph
+    NG = 20
+
+    def captured(fn):
+        fn()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(NG):
+                fn()
+        return g
+
+    graphs = {dt: [captured(lambda: m(B, out=outs[dt])), captured(lambda: (m(B, out=outs[dt]), m.advance())), captured(lambda: outs[dt].fill_(0.5))]
+              for dt, m in mods.items()}
+    for rnd in range(3):
+        th = host_ms()
+        for dt, m in mods.items():
+            out, nbytes = outs[dt], outs[dt].numel() * outs[dt].element_size()
+            te = timeit(lambda: (m(B, out=out), m.advance()), reps=200, warm=5)
+            tk, ts, tf = (timeit(g.replay, reps=20, warm=2) / NG for g in graphs[dt])
+            print(f"zenith {str(dt)[6:]:8s} round {rnd}: kernel {tk * 1e3:7.2f} us = {nbytes / tk / 1e9:5.2f} TB/s = {nbytes / (tk * 1e-3) / PEAK * 100:5.1f} % "
+                  f"of the HBM write roof ({nbytes / 1e6:.1f} MB) | + advance {ts * 1e3:7.2f} us | fill_ {tf * 1e3:7.2f} us (all three: {NG} "
+                  f"in a captured graph) | eager kernel + advance {te * 1e3:7.2f} us | host numpy + upload {th:7.3f} ms = "
+                  f"{th / ts:6.0f} x kernel + advance", flush=True)
 
 
 if __name__ == "__main__":
