@@ -436,6 +436,30 @@ int mk_crps(const void* f, int f_dtype, const void* obs, int o_dtype, const floa
 int mk_crps_complex(const void* f, const void* obs, const float* q, const float* w, const float* gout, float* partial, void* gf,
                     int B, int E, int C, long long hw, float alpha, int grad, void* stream);
 
+/* ---- kernel score: DISCO-filtered ensemble CRPS (KernelScoreLoss, makani/utils/losses/crps_loss.py:1022-1247;
+ * makani_amd/csrc/kscore.hip).  Members f (B, E, C, H, W) and observation obs (B, C, H, W), f32 | bf16 each, are filtered by the K
+ * basis functions of a DISCO convolution with in_shape == out_shape and scored pointwise; the filtered fields exist in registers only.
+ * The filter comes as chunks: desc (n, 4) int32 {input row, first longitude, taps (a multiple of 4, at most mk_kscore_chunk()), offset
+ * into vals of the chunk's [K][taps] f32 values}, doff (H + 1) int32 the chunks of every output row; the taps of a chunk read the
+ * longitudes first + l + p (mod W) for output longitude p.  q (H W) quadrature weights; w optional f32 spatial weights addressed as
+ * w[b w_sb + (c K + k) w_sc + t W + p] (a stride of 0 broadcasts).  type: 0 skillspread, 1 probability weighted moment, 2 naive
+ * skillspread, 4 cdf (ens_w (E) optional); E = 1 scores |o - f|.  1 <= E <= 32.
+ *   mk_kscore_fwd: out (B C) f32 = sum over k and the points of q w crps; partial: B C mk_kscore_partials(K, H, W) floats of scratch.
+ *   mk_kscore_bwd: gx (shape / dtype of f) from gout (B C) f32; desc_t / doff_t / vals_t the chunks of the transposed filter (segments
+ *       = input rows, rows = output rows, longitudes negated); ws: mk_kscore_workspace(B C, E, K, H, W) floats, which hold the score
+ *       gradients (P, E, K, H, W) of P = mk_kscore_planes(...) planes at a time (at most 640 MiB, at least one plane). */
+int mk_kscore_chunk(void);
+long long mk_kscore_partials(int K, int H, int W);
+int mk_kscore_planes(int planes, int E, int K, int H, int W);
+long long mk_kscore_workspace(int planes, int E, int K, int H, int W);
+int mk_kscore_fwd(const void* f, int f_dtype, const void* obs, int o_dtype, const int* desc, const int* doff, const float* vals,
+                  const float* q, const float* w, long long w_sb, long long w_sc, float* partial, float* out, int B, int E, int C, int K,
+                  int H, int W, int type, float alpha, const float* ens_w, void* stream);
+int mk_kscore_bwd(const void* f, int f_dtype, const void* obs, int o_dtype, const int* desc, const int* doff, const float* vals,
+                  const int* desc_t, const int* doff_t, const float* vals_t, const float* q, const float* w, long long w_sb, long long w_sc,
+                  const float* gout, float* ws, void* gx, int B, int E, int C, int K, int H, int W, int type, float alpha,
+                  const float* ens_w, void* stream);
+
 /* ---- ensemble energy scores (grid Lp, Sobolev, per-degree spectral L2) ------------------------------------------------
  * Replace the pair tensors of makani/utils/losses/energy_score.py:30-652 (LpEnergyScoreLoss, SobolevEnergyScoreLoss,
  * SpectralL2EnergyScoreLoss) and their autograd; three stages (makani_amd/csrc/escore.hip).

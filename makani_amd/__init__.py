@@ -10,7 +10,7 @@ from .losses import CRPSLoss, GradientCRPSLoss, VortDivCRPSLoss, GeometricLpLoss
 from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss, SpectralL2EnergyScoreLoss
 from .losses import SpectralAMSELoss, EnsembleNLLLoss, GaussianMMDLoss
 from .losses import SpectralCoherenceLoss, CoherenceRegularization, SpectralRegularization, EnsembleGramFn
-from .losses import HydrostaticBalanceLoss, DriftRegularization, LossHandler
+from .losses import HydrostaticBalanceLoss, DriftRegularization, LossHandler, KernelScoreLoss
 from .metrics import (GeometricL1, GeometricRMSE, GeometricACC, GeometricSpread, GeometricSSR, GeometricCRPS, GeometricRankHistogram,
                       deterministic_sums)
 from .metric import MetricsHandler, MetricRollout, Quadrature, SimpsonQuadrature, TrapezoidQuadrature
@@ -35,7 +35,7 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
            "SpectralAMSELoss", "EnsembleNLLLoss", "GaussianMMDLoss",
            "SpectralCoherenceLoss", "CoherenceRegularization", "SpectralRegularization", "EnsembleGramFn",
-           "HydrostaticBalanceLoss", "DriftRegularization", "LossHandler",
+           "HydrostaticBalanceLoss", "DriftRegularization", "LossHandler", "KernelScoreLoss",
            "GeometricL1", "GeometricRMSE", "GeometricACC", "GeometricSpread", "GeometricSSR", "GeometricCRPS", "GeometricRankHistogram",
            "deterministic_sums", "MetricsHandler", "MetricRollout", "Quadrature", "SimpsonQuadrature", "TrapezoidQuadrature",
            "BaseNoiseS2", "IsotropicGaussianRandomFieldS2", "DiffusionNoiseS2", "DummyNoiseS2", "InputNoise", "build_noise",

@@ -205,6 +205,47 @@ def convolution_tensor(in_shape, out_shape, kernel_shape, basis_type="morlet", g
     return dict(k=k.astype(np.int64), t=t.astype(np.int64), i=i.astype(np.int64), j=j.astype(np.int64), v=v, K=K, live=live)
 
 
+def kscore_chunks(psi, shape, chunk, transposed=False):
+    """the convolution tensor ``psi`` of a grid ``shape = (H, W)`` onto itself in the chunk form of csrc/kscore.hip: per (segment,
+    row) the longitudes of ALL basis functions are covered by one circular run (the whole circle near the poles), cut into pieces
+    of at most ``chunk`` taps, each zero-padded to a multiple of four.  -> (desc (n, 4) int32 {row, first longitude, taps, value
+    offset}, doff (H + 1) int32, vals float32 with [K][taps] values per chunk).  Segments are the output rows and rows the input
+    rows; ``transposed``: the adjoint's lists (segments = input rows, rows = output rows, longitudes negated)."""
+    H, W = shape
+    K = psi["K"]
+    k, v = psi["k"], psi["v"]
+    seg, row, lon = (psi["i"], psi["t"], (-psi["j"]) % W) if transposed else (psi["t"], psi["i"], psi["j"])
+    order = np.lexsort((lon, row, seg))
+    k, v, seg, row, lon = k[order], v[order], seg[order], row[order], lon[order]
+    key = seg * H + row
+    first = np.flatnonzero(np.r_[True, key[1:] != key[:-1]]) if key.size else np.zeros(0, np.int64)
+    last = np.r_[first[1:], key.size]
+    desc, vals, counts, voff = [], [], np.zeros(H, np.int64), 0
+    for a, b in zip(first, last):
+        ul = np.unique(lon[a:b])
+        if ul.size == W:
+            j0, L = 0, W
+        else:                                    # the run starts behind the largest gap of the circle
+            gaps = np.diff(np.r_[ul, ul[0] + W])
+            g = int(np.argmax(gaps))
+            j0, L = int(ul[(g + 1) % ul.size]), int(W - gaps[g] + 1)
+        dense = np.zeros((K, L), np.float32)
+        dense[k[a:b], (lon[a:b] - j0) % W] = v[a:b]
+        for c0 in range(0, L, chunk):
+            n = min(chunk, L - c0)
+            npad = (n + 3) // 4 * 4
+            blk = np.zeros((K, npad), np.float32)
+            blk[:, :n] = dense[:, c0:c0 + n]
+            desc.append((int(row[a]), (j0 + c0) % W, npad, voff))
+            vals.append(blk.reshape(-1))
+            voff += blk.size
+            counts[seg[a]] += 1
+    doff = np.zeros(H + 1, np.int64)
+    doff[1:] = np.cumsum(counts)
+    return (np.array(desc, np.int32).reshape(-1, 4), doff.astype(np.int32),
+            np.concatenate(vals) if vals else np.zeros(0, np.float32))
+
+
 _PSI_CACHE = {}          # constructor arguments -> convolution tensor (FourCastNet3's eight local blocks share one)
 _LIST_CACHE = {}         # (constructor arguments, device) -> device lists
 

@@ -530,6 +530,84 @@ class CRPSLoss(_EnsembleLoss):
         return self._sum_shares(crps, groups)
 
 
+class KernelScoreLoss(_EnsembleLoss):
+    """``KernelScoreLoss`` of ``makani/utils/losses/crps_loss.py:1022-1247``, the kernel score of Gneiting and Raftery (2007) with
+    the basis functions of a DISCO convolution as kernels: members and observation are filtered by every basis function (a
+    depthwise convolution with a 0 / 1 selection weight, ``theta_cutoff = 2 kernel_shape[0] pi / (H - 1)``), the filtered fields are
+    scored by the pointwise ensemble CRPS and summed over the basis functions: ``forward(forecasts (B, E, C, H, W), observations
+    (B, C, H, W), spatial_weights=None) -> (B, C)``.  Stencil and score are ONE HIP kernel (``csrc/kscore.hip``): the filtered
+    ensemble (B E, C K, H, W) of the reference is never formed; backward recomputes it and keeps only a capped workspace.
+
+    Built: ``crps_type`` "skillspread" (default) and "naive skillspread" (with ``alpha``), "probability weighted moment" and "cdf"
+    (with ``ensemble_weights``); 1 <= E <= 32 (E = 1: ``|o - f|``); ``spatial_weights`` of batch extent 1 or B and channel extent
+    1 or C K.  Deviations from the reference, stated: its default ``kernel_basis_type="harmonic"`` and ``kernel_basis_norm_mode=
+    "nodal"`` are refused with the messages of ``makani_amd.disco`` (built are the bases and norm modes of ``convolution_tensor``:
+    pass e.g. "morlet" / "mean"); a live "spatial" or "ensemble" group with ``spatial_distributed`` / ``ensemble_distributed`` raises
+    ``NotImplementedError`` (this is the serial path); CPU tensors raise; non-finite ``ensemble_weights`` are rejected."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, crps_type: str = "skillspread",
+                 spatial_distributed: Optional[bool] = False, ensemble_distributed: Optional[bool] = False,
+                 ensemble_weights: Optional[torch.Tensor] = None, alpha: Optional[float] = 1.0, eps: Optional[float] = 1.0e-6,
+                 kernel_basis_type: str = "harmonic", kernel_basis_norm_mode: str = "nodal", kernel_shape: Tuple[int, int] = (3, 3),
+                 **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, spatial_distributed, ensemble_distributed)
+        if self.spatial_distributed or self.ensemble_distributed:
+            raise NotImplementedError("KernelScoreLoss: the spatially and the ensemble distributed forms are not built (serial path only)")
+        if crps_type not in ("skillspread", "naive skillspread", "probability weighted moment", "cdf"):
+            raise ValueError(f"Unknown CRPS crps_type {crps_type}")
+        if crps_type not in ("skillspread", "naive skillspread") and alpha < 1.0:
+            raise NotImplementedError("The alpha parameter (almost fair CRPS factor) is only supported for the skillspread kernels.")
+        if ensemble_weights is not None and crps_type not in ("cdf", "probability weighted moment"):
+            raise NotImplementedError("currently only constant ensemble weights are supported")
+        _check_finite_weights(ensemble_weights)
+        if tuple(crop_shape) != tuple(img_shape) or tuple(crop_offset) != (0, 0):
+            raise ValueError("KernelScoreLoss filters the whole grid: crop_shape must equal img_shape")
+        self.crps_type, self.alpha, self.eps = crps_type, alpha, eps
+        self.register_buffer("ensemble_weights", None if ensemble_weights is None else ensemble_weights.float().reshape(-1).contiguous(),
+                             persistent=False)
+        from . import disco
+        ks0 = kernel_shape if isinstance(kernel_shape, int) else kernel_shape[0]
+        self.kernel_shape, self.kernel_basis_size = disco.basis_layout(kernel_basis_type, kernel_shape)
+        self.theta_cutoff = 2 * ks0 * math.pi / float(img_shape[0] - 1)
+        psi = disco.convolution_tensor(tuple(img_shape), tuple(img_shape), self.kernel_shape, basis_type=kernel_basis_type,
+                                       grid_in=grid_type, grid_out=grid_type, theta_cutoff=self.theta_cutoff,
+                                       basis_norm_mode=kernel_basis_norm_mode)
+        ch = lib().mk_kscore_chunk()
+        self._chunks = tuple(tuple(torch.from_numpy(a) for a in disco.kscore_chunks(psi, tuple(img_shape), ch, transposed=tr))
+                             for tr in (False, True))
+        self._device_chunks = {}
+
+    def _lists(self, device):
+        if device not in self._device_chunks:
+            self._device_chunks[device] = tuple(tuple(a.to(device) for a in c) for c in self._chunks)
+        return self._device_chunks[device]
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, spatial_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        self._check(forecasts, observations, spatial_weights)
+        B, E, Cc, H, W = forecasts.shape
+        ensemble_size_check(E, "kernel-score")
+        if (H, W) != tuple(self.img_shape):
+            raise ValueError(f"forecasts on a {H} x {W} grid, the loss was built for {tuple(self.img_shape)}")
+        K = self.kernel_basis_size
+        wgt = None
+        if spatial_weights is not None:
+            Bw, Cw = spatial_weights.shape[:2]
+            if Bw not in (1, B) or Cw not in (1, Cc * K) or tuple(spatial_weights.shape[2:]) != (H, W):
+                raise ValueError(f"spatial_weights of shape {tuple(spatial_weights.shape)}: expected batch extent 1 or {B}, channel "
+                                 f"extent 1 or {Cc * K} (channels x basis functions) and the grid {H} x {W}")
+            wgt = (spatial_weights.float().contiguous(), Cw * H * W if (Bw == B and B > 1) else 0, H * W if Cw == Cc * K else 0)
+        need_gpu(forecasts)
+        fwd, bwd = self._lists(forecasts.device)
+        ew = _ens_w(self.ensemble_weights, E, self.crps_type) if E > 1 else None
+        from . import ops
+        return ops.KScoreFn.apply(forecasts, observations, fwd, bwd, K, self.quad_weight_split.reshape(-1), wgt,
+                                  _CRPS_TYPES[self.crps_type], self.alpha, ew)
+
+
 def _sht_pair(sht, forecasts, observations):
     """the coefficients of members and observation as the spectral ensemble losses take them: fp32, autocast off, / sqrt(4 pi)"""
     with torch.autocast(device_type=forecasts.device.type, enabled=False):

@@ -2330,3 +2330,39 @@ class LossPrepFn(torch.autograd.Function):
         g_prd = torch.empty(shape, dtype=dt, device=next(g for g in gs if g is not None).device)
         check(lib().mk_loss_prep_bwd(ptr(gs[0]), ptr(gs[1]), ptr(gs[2]), ptr(g_prd), dtype_code(g_prd), inv, B, E, n, stream()), "mk_loss_prep_bwd")
         return (g_prd if dt == dtype_in else g_prd.to(dtype_in)), None, None, None, None
+
+
+class KScoreFn(torch.autograd.Function):
+    """out[b, c] = sum_{k, t, p} q w crps(psi_k (*) obs, psi_k (*) members) (``csrc/kscore.hip``): forecasts (B, E, C, H, W) and
+    obs (B, C, H, W) f32 | bf16, ``chunks`` / ``chunks_t`` the device lists of the filter and of its transpose (``disco.kscore_chunks``:
+    desc, doff, vals), q (H W), wgt None or ((Bw, Cw, H, W) f32 contiguous, batch stride, channel stride).  The filtered fields live
+    in registers; backward recomputes them and pushes the score gradients of a bounded group of planes at a time back through
+    the transposed filter.  The gradient goes to the forecasts alone."""
+
+    @staticmethod
+    def forward(ctx, forecasts, obs, chunks, chunks_t, K, q, wgt, ctype, alpha, ens_w=None):
+        _lib.need_gpu(forecasts, "losses")
+        B, E, Cc, H, W = forecasts.shape
+        f, o = _lib.prep(forecasts), _lib.prep(obs)
+        w, w_sb, w_sc = wgt if wgt is not None else (None, 0, 0)
+        partial = torch.empty((B * Cc, lib().mk_kscore_partials(K, H, W)), dtype=torch.float32, device=f.device)
+        out = torch.empty((B, Cc), dtype=torch.float32, device=f.device)
+        check(lib().mk_kscore_fwd(ptr(f), dtype_code(f), ptr(o), dtype_code(o), ptr(chunks[0]), ptr(chunks[1]), ptr(chunks[2]), ptr(q),
+                                  ptr(w), w_sb, w_sc, ptr(partial), ptr(out), B, E, Cc, K, H, W, ctype, float(alpha), ptr(ens_w),
+                                  stream()), "mk_kscore_fwd")
+        ctx.save_for_backward(f, o, q)
+        ctx.meta = (chunks, chunks_t, K, (w, w_sb, w_sc), ctype, float(alpha), ens_w, forecasts.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        f, o, q = ctx.saved_tensors
+        chunks, chunks_t, K, (w, w_sb, w_sc), ctype, alpha, ens_w, dt = ctx.meta
+        B, E, Cc, H, W = f.shape
+        gx = torch.empty_like(f)
+        go = g.float().contiguous()
+        ws = torch.empty((lib().mk_kscore_workspace(B * Cc, E, K, H, W),), dtype=torch.float32, device=f.device)
+        check(lib().mk_kscore_bwd(ptr(f), dtype_code(f), ptr(o), dtype_code(o), ptr(chunks[0]), ptr(chunks[1]), ptr(chunks[2]),
+                                  ptr(chunks_t[0]), ptr(chunks_t[1]), ptr(chunks_t[2]), ptr(q), ptr(w), w_sb, w_sc, ptr(go), ptr(ws),
+                                  ptr(gx), B, E, Cc, K, H, W, ctype, alpha, ptr(ens_w), stream()), "mk_kscore_bwd")
+        return gx.to(dt), None, None, None, None, None, None, None, None, None

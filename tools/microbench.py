@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31] [zenith]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31] [zenith] [kscore]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -1144,6 +1144,60 @@ def zenith():
                   f"of the HBM write roof ({nbytes / 1e6:.1f} MB) | + advance {ts * 1e3:7.2f} us | fill_ {tf * 1e3:7.2f} us (all three: {NG} "
                   f"in a captured graph) | eager kernel + advance {te * 1e3:7.2f} us | host numpy + upload {th:7.3f} ms = "
                   f"{th / ts:6.0f} x kernel + advance", flush=True)
+
+
+def kscore():
+    """KernelScoreLoss forward + backward at (B, E, C, H, W) = (1, 16, 73, 721, 1440), 3 x 3 Morlet basis, bf16 and f32 forecasts
+    (csrc/kscore.hip), beside the composition on the existing kernels: DiscreteContinuousConvS2(groups = C) with the 0 / 1 selection
+    weight on members and observation, then CRPSLoss on the C K filtered channels, run over MICROBENCH_KSCORE_SLICE (default 24)
+    channels at a time (the filtered members of 24 channels are 14 GB in fp32).  MICROBENCH_KSCORE_C (default 73) shrinks the
+    channel count, MICROBENCH_KSCORE_REPS (default 3) sets the timed runs; one warm-up run each."""
+    B, E, H, W = 1, 16, 721, 1440
+    C = int(os.environ.get("MICROBENCH_KSCORE_C", "73"))
+    CS = min(C, int(os.environ.get("MICROBENCH_KSCORE_SLICE", "24")))
+    reps = int(os.environ.get("MICROBENCH_KSCORE_REPS", "3"))
+    names = [f"c{i}" for i in range(C)]
+    t0 = time.perf_counter()
+    loss = ma.KernelScoreLoss((H, W), (H, W), (0, 0), names, "equiangular", kernel_basis_type="morlet", kernel_basis_norm_mode="mean",
+                              kernel_shape=(3, 3)).to(dev)
+    K = loss.kernel_basis_size
+    print(f"kscore: filter lists built on the host in {time.perf_counter() - t0:.1f} s; {loss._chunks[0][0].shape[0]} forward chunks, "
+          f"workspace {ma._lib.lib().mk_kscore_workspace(B * C, E, K, H, W) * 4 / 2**20:.0f} MiB "
+          f"({ma._lib.lib().mk_kscore_planes(B * C, E, K, H, W)} plane(s) per pass)", flush=True)
+    conv = ma.DiscreteContinuousConvS2(CS, CS * K, (H, W), (H, W), (3, 3), basis_type="morlet", basis_norm_mode="mean", groups=CS,
+                                       bias=False, theta_cutoff=loss.theta_cutoff).to(dev)
+    with torch.no_grad():
+        conv.weight.zero_()
+        for i in range(CS * K):
+            conv.weight[i, 0, i % K] = 1.0
+    conv.weight.requires_grad_(False)
+    crps = ma.CRPSLoss((H, W), (H, W), (0, 0), [f"k{i}" for i in range(CS * K)], "equiangular").to(dev)
+    for dt in (torch.bfloat16, torch.float32):
+        f = torch.randn(B, E, C, H, W, device=dev, dtype=dt).requires_grad_(True)
+        o = torch.randn(B, C, H, W, device=dev)
+
+        def fused():
+            f.grad = None
+            loss(f, o).sum().backward()
+
+        def composed():
+            f.grad = None
+            for c0 in range(0, C - CS + 1, CS):           # whole slices (the module is built for CS channels)
+                yf = conv(f[:, :, c0:c0 + CS].reshape(B * E, CS, H, W)).reshape(B, E, CS * K, H, W)
+                yo = conv(o[:, c0:c0 + CS].to(dt))
+                crps(yf, yo).sum().backward()
+
+        torch.cuda.reset_peak_memory_stats()
+        tf_ = timeit(fused, reps=reps, warm=1)
+        mf = torch.cuda.max_memory_allocated() / 2**30
+        torch.cuda.reset_peak_memory_stats()
+        tc = timeit(composed, reps=reps, warm=1)
+        mc = torch.cuda.max_memory_allocated() / 2**30
+        done = C // CS * CS
+        print(f"kscore {str(dt)[6:]:8s} C = {C}: fused fwd + bwd {tf_:9.1f} ms ({tf_ / C:7.2f} ms / channel, peak {mf:6.1f} GiB) | composition "
+              f"{CS} channels at a time over {done} channels {tc:9.1f} ms ({tc / done:7.2f} ms / channel, peak {mc:6.1f} GiB) | "
+              f"per channel fused / composition = {(tf_ / C) / (tc / done):5.2f}; {reps} runs each", flush=True)
+        del f, o
 
 
 if __name__ == "__main__":
