@@ -486,6 +486,23 @@ int mk_escore_grad(const void* f, int kind, const void* obs, const float* q, con
  * table (B, Cout, 1, K) = d loss / d sums. */
 int mk_mmd_finish(const float* sums, float* loss, float* table, int B, int E, int C, int reduce, float sigma, float alpha, void* stream);
 
+/* ---- corrected per-degree spectral L2 energy score (CorrectedSpectralL2EnergyScoreLoss, makani/utils/losses/energy_score.py:
+ * 859-1042; makani_amd/csrc/escorr.hip): the per-degree energy score with the spread term scaled by pow_o / (P_pred + eps).
+ * f: (B, E, C, L, M) complex64 members (re, im interleaved), obs: (B, C, L, M) complex64, q: (L, M) f32 weights; 1 <= E <= 32.
+ * K' = E + E (E - 1) / 2 + E + 1 sums per (b, c, l): [0, E) skill_e = sum_m q mask |o - f_e|^2; then spread_ij (i < j,
+ * lexicographic) = sum_m q mask |f_i - f_j|^2; then pow_e = sum_m q |f_e|^2; last pow_o = sum_m q |o|^2.  mask: 0 where the
+ * observation or any member is NaN; NaN values count as 0 (the powers are NOT masked).
+ * mk_escorr_sums:   sums (B, C, L, K') f32.  One block per row, every coefficient read once; no workspace.
+ * mk_escorr_finish: sums -> lossl (B, Cout, L) = eskill - espread ratio / 2 per degree, loss (B, Cout) = their sum in l order, and
+ *                   table (B, Cout, L, K' + 1) = d loss / d (each sum), 0 where a distance is below eps, with d loss / d P_pred
+ *                   in column K'.  Cout = reduce ? 1 : C (channels summed in order).
+ * mk_escorr_grad:   gf (B, E, C, L, M) complex64 = gout[b][co] d loss / d f in torch's convention (d |z|^2 = 2 z); 0 at NaN inputs. */
+int mk_escorr_sums(const float* f, const float* obs, const float* q, float* sums, int B, int E, int C, int L, int M, void* stream);
+int mk_escorr_finish(const float* sums, float* loss, float* lossl, float* table, int B, int E, int C, int L, int reduce, float beta,
+                     float alpha, float eps, void* stream);
+int mk_escorr_grad(const float* f, const float* obs, const float* q, const float* table, const float* gout, float* gf, int B, int E,
+                   int C, int Cout, int L, int M, void* stream);
+
 /* ---- adjusted mean squared error in spectral space (SpectralAMSELoss, makani/utils/losses/amse_loss.py:29-114) --------
  * X, Y: (R, L, M) complex64 coefficient planes (re, im interleaved); wgt: optional (R, L, M) f32.  c_m = 1 for the global order
  * m + m_off = 0, else 2; orders m > l + tri_off are structurally zero (tri_off = l_off - m_off of a shard).

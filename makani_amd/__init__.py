@@ -8,6 +8,7 @@ from .layers import MLP, EncoderDecoder, InstanceNorm2d, PointwiseConv, Geometri
 from .sfno import SphericalFourierNeuralOperatorNet, NeuralOperatorBlock, SpectralFilterLayer
 from .losses import CRPSLoss, GradientCRPSLoss, VortDivCRPSLoss, GeometricLpLoss, GridQuadrature, SpectralCRPSLoss, SpectralLpLoss, SpectralH1Loss
 from .losses import LpEnergyScoreLoss, L2EnergyScoreLoss, SobolevEnergyScoreLoss, SpectralL2EnergyScoreLoss
+from .losses import CorrectedSpectralL2EnergyScoreLoss
 from .losses import SpectralAMSELoss, EnsembleNLLLoss, GaussianMMDLoss
 from .losses import SpectralCoherenceLoss, CoherenceRegularization, SpectralRegularization, EnsembleGramFn
 from .losses import HydrostaticBalanceLoss, DriftRegularization, LossHandler, KernelScoreLoss
@@ -33,6 +34,7 @@ __all__ = ["RealSHT", "InverseRealSHT", "RealVectorSHT", "InverseRealVectorSHT",
            "GridQuadrature", "SpectralLpLoss", "SpectralH1Loss", "CRPSLoss", "SpectralCRPSLoss", "GeometricInstanceNormS2", "MultiStepWrapper", "SingleStepWrapper",
            "DiscreteContinuousConvS2", "ResampleS2", "AtmoSphericNeuralOperatorNet",
            "LpEnergyScoreLoss", "L2EnergyScoreLoss", "SobolevEnergyScoreLoss", "SpectralL2EnergyScoreLoss",
+           "CorrectedSpectralL2EnergyScoreLoss",
            "SpectralAMSELoss", "EnsembleNLLLoss", "GaussianMMDLoss",
            "SpectralCoherenceLoss", "CoherenceRegularization", "SpectralRegularization", "EnsembleGramFn",
            "HydrostaticBalanceLoss", "DriftRegularization", "LossHandler", "KernelScoreLoss",

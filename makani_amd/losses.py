@@ -1163,6 +1163,85 @@ class SpectralL2EnergyScoreLoss(_SpectralEnergyScore):
         return self._score(forecasts, observations, per_degree=True)
 
 
+class CorrectedEnergyScoreFn(torch.autograd.Function):
+    """The three stages of ``csrc/escorr.hip``.  forecasts (B, E, C, L, M) complex, obs (B, C, L, M) complex, q (L, M):
+    ``mk_escorr_sums`` -> sums (B, C, L, K'), K' = E + E (E - 1) / 2 + E + 1 (skills, spreads, member powers, the observation's
+    power), added over ``sum_groups`` (distances and powers are plain sums: ONE all-reduce in the place of the reference's
+    four); ``mk_escorr_finish`` -> loss (B, C_out) and the table d loss / d sums, kept for ``mk_escorr_grad``.  Gradient with
+    respect to the forecasts only."""
+
+    @staticmethod
+    def forward(ctx, forecasts, obs, q, reduce, beta, alpha, eps, sum_groups):
+        B, E, Cc, L, M = forecasts.shape
+        f = torch.view_as_real(forecasts.to(torch.complex64).contiguous())
+        o = torch.view_as_real(obs.to(torch.complex64).contiguous())
+        q = q.float().contiguous()
+        K = E + E * (E - 1) // 2 + E + 1
+        sums = torch.empty((B, Cc, L, K), dtype=torch.float32, device=f.device)
+        check(lib().mk_escorr_sums(ptr(f), ptr(o), ptr(q), ptr(sums), B, E, Cc, L, M, stream()), "mk_escorr_sums")
+        from . import ops
+        for group in sum_groups:
+            ops._all_reduce_sum(sums, group)
+        Cout = 1 if reduce else Cc
+        loss = torch.empty((B, Cout), dtype=torch.float32, device=f.device)
+        lossl = torch.empty((B, Cout, L), dtype=torch.float32, device=f.device)
+        table = torch.empty((B, Cout, L, K + 1), dtype=torch.float32, device=f.device)
+        check(lib().mk_escorr_finish(ptr(sums), ptr(loss), ptr(lossl), ptr(table), B, E, Cc, L, int(reduce), float(beta), float(alpha),
+                                     float(eps), stream()), "mk_escorr_finish")
+        ctx.save_for_backward(f, o, q, table)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        f, o, q, table = ctx.saved_tensors
+        B, E, Cc, L, M = f.shape[:5]
+        gf = torch.empty_like(f)
+        go = g.float().contiguous()
+        check(lib().mk_escorr_grad(ptr(f), ptr(o), ptr(q), ptr(table), ptr(go), ptr(gf), B, E, Cc, table.shape[1], L, M, stream()),
+              "mk_escorr_grad")
+        return (torch.view_as_complex(gf),) + (None,) * 7
+
+
+class CorrectedSpectralL2EnergyScoreLoss(_SpectralEnergyScore):
+    """``CorrectedSpectralL2EnergyScoreLoss`` of ``makani/utils/losses/energy_score.py:859-1042``: the per-degree spectral L2
+    energy score whose spread term is scaled by P_true / (P_pred + eps), the observation's power spectrum over the ensemble
+    mean of the members' — inflating the power and decorrelating the phases no longer lowers the score.  The spectra are not
+    NaN-masked (a NaN coefficient counts as 0 there), the distances are, as in the reference.  ``forward(forecasts (B, E, C, H,
+    W), observations (B, C, H, W)) -> (B, C) | (B, 1)`` on the row-resident kernels of ``csrc/escorr.hip``.  The reference's
+    ``LossHandler`` does not register the class, and neither does the registry here.
+
+    Deviations, stated: no gradient for the observations, a given ``ensemble_weights`` raises, 1 <= E <= 32."""
+
+    def __init__(self, img_shape: Tuple[int, int], crop_shape: Tuple[int, int], crop_offset: Tuple[int, int],
+                 channel_names: List[str], grid_type: str, lmax: Optional[int] = None, spatial_distributed: Optional[bool] = False,
+                 ensemble_distributed: Optional[bool] = False, ensemble_weights: Optional[torch.Tensor] = None,
+                 channel_reduction: Optional[bool] = True, alpha: Optional[float] = 1.0, beta: Optional[float] = 1.0,
+                 eps: Optional[float] = 1.0e-6, **kwargs):
+        super().__init__(img_shape, crop_shape, crop_offset, channel_names, grid_type, lmax, spatial_distributed,
+                         ensemble_distributed, ensemble_weights, channel_reduction, alpha, beta, eps)
+
+    @torch.compiler.disable(recursive=True)
+    @device_guard
+    def forward(self, forecasts: torch.Tensor, observations: torch.Tensor, ensemble_weights: Optional[torch.Tensor] = None,
+                **kwargs) -> torch.Tensor:
+        from . import comm as _comm
+        _escore_checks(forecasts, self.ensemble_weights)
+        need_gpu(forecasts)
+        f, o = _sht_pair(self.sht, forecasts, observations)
+        q = self.lm_weights
+        groups = []
+        if self.ensemble_distributed:               # members <-> a share of the orders m (:950-960)
+            f, o, q, group = self._ensemble_split_lm(f, o, q)
+            groups.append(group)
+        if self.spatial_distributed and _comm.get_size("w") > 1:          # the orders are summed over "w", the degrees over "h"
+            groups.append(_comm.get_group("w"))
+        ensemble_size_check(f.shape[1], "energy-score")
+        loss = CorrectedEnergyScoreFn.apply(f, o, q, self.channel_reduction, self.beta, self.alpha, self.eps, groups)
+        if self.spatial_distributed and _comm.get_size("h") > 1:
+            loss = ReduceFromGroupFn.apply(loss, _comm.get_group("h"))
+        return loss
+
+
 # --------------------------------------------------------------------------- #
 # adjusted MSE, ensemble likelihood, Gaussian MMD (makani/utils/losses/amse_loss.py, likelihood_loss.py, mmd_loss.py)
 # --------------------------------------------------------------------------- #

@@ -1,5 +1,5 @@
 """Per-kernel microbenchmarks at the BASELINE shapes (HIP events on the launch stream).
-   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31] [zenith] [kscore]"""
+   python tools/microbench.py [fft] [legendre] [dhconv] [pointwise] [vsht] [escore] [noise] [noise_shard] [losses] [coherence] [metrics] [preproc] [constraints] [interpolant] [losshandler] [mhandler] [fcn31] [zenith] [kscore] [escorr]"""
 import os, sys, time, math, json
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -1198,6 +1198,91 @@ def kscore():
               f"{CS} channels at a time over {done} channels {tc:9.1f} ms ({tc / done:7.2f} ms / channel, peak {mc:6.1f} GiB) | "
               f"per channel fused / composition = {(tf_ / C) / (tc / done):5.2f}; {reps} runs each", flush=True)
         del f, o
+
+
+def escorr():
+    """The row-resident kernels of csrc/escorr.hip on coefficients (1, E, 73, 721, 721) complex64, E = 4, 16, 32, beside the tiled
+    mk_escore_sums (mask pre-pass and combine included) / mk_escore_grad in spectral mode on the same tensor: three alternating
+    runs each, the share of HBM peak on ALGORITHMIC traffic ((E + 1) rows read forward, (E + 1) read + E written backward).
+    Then the modules at 721 x 1440, C = 73, E = 16, bf16 input, forward + backward: CorrectedSpectralL2EnergyScoreLoss beside
+    SpectralL2EnergyScoreLoss, and (E = 4, on the coefficients) the reference's broadcast formulation in torch."""
+    from makani_amd._lib import lib, ptr, stream, check
+    from makani_amd.losses import CorrectedEnergyScoreFn
+    PEAK = 8.0e12
+    B, C, L, M = 1, 73, 721, 721
+    q = torch.rand(L, M, device=dev) / (L * M)
+    pct = lambda nbytes, ms: nbytes / (ms * 1e-3) / PEAK * 100
+    fmt = lambda ts: f"{min(ts):7.3f} ms (3 runs, spread {100 * (max(ts) - min(ts)) / min(ts):4.1f} %)"
+    for E in (4, 16, 32):
+        f = torch.view_as_real(torch.randn(B, E, C, L, M, dtype=torch.complex64, device=dev))
+        o = torch.view_as_real(torch.randn(B, C, L, M, dtype=torch.complex64, device=dev))
+        K0 = E + E * (E - 1) // 2
+        K = K0 + E + 1
+        sums, sums0 = torch.empty(B, C, L, K, device=dev), torch.empty(B, C, L, K0, device=dev)
+        ws = torch.empty(lib().mk_escore_sums_workspace(B, E, C, L * M, L, 1), device=dev)
+        loss, lossl = torch.empty(B, 1, device=dev), torch.empty(B, 1, L, device=dev)
+        table, table0 = torch.empty(B, 1, L, K + 1, device=dev), torch.empty(B, 1, L, K0, device=dev)
+        gout, gf = torch.ones(B, 1, device=dev), torch.empty_like(f)
+        runs = {
+            "escorr sums": lambda: check(lib().mk_escorr_sums(ptr(f), ptr(o), ptr(q), ptr(sums), B, E, C, L, M, stream())),
+            "escore sums": lambda: check(lib().mk_escore_sums(ptr(f), 2, ptr(o), ptr(q), None, ptr(sums0), ptr(ws), B, E, C, L * M, L, 1, 2.0,
+                                                              stream())),
+            "escorr finish": lambda: check(lib().mk_escorr_finish(ptr(sums), ptr(loss), ptr(lossl), ptr(table), B, E, C, L, 1, 1.0, 1.0, 1e-6,
+                                                                  stream())),
+            "escore finish": lambda: check(lib().mk_escore_finish(ptr(sums0), None, 0, ptr(loss), ptr(table0), B, E, C, L, 1, 2.0, 1.0, 1.0,
+                                                                  1e-6, stream())),
+            "escorr grad": lambda: check(lib().mk_escorr_grad(ptr(f), ptr(o), ptr(q), ptr(table), ptr(gout), ptr(gf), B, E, C, 1, L, M, stream())),
+            "escore grad": lambda: check(lib().mk_escore_grad(ptr(f), 2, ptr(o), ptr(q), None, ptr(table0), ptr(gout), ptr(gf), B, E, C, 1, L * M,
+                                                              L, 1, 2.0, stream())),
+        }
+        times = {k: [] for k in runs}
+        for _ in range(3):                      # alternating
+            for k, fn in runs.items():
+                times[k].append(timeit(fn, reps=5, warm=1))
+        nb = {"sums": C * L * M * (E + 1) * 8, "grad": C * L * M * (2 * E + 1) * 8}
+        for k, ts in times.items():
+            share = f" {pct(nb[k.split()[1]], min(ts)):5.1f} % of HBM peak" if k.split()[1] in nb else ""
+            print(f"E={E:2d} {k:14s} {fmt(ts)}{share}", flush=True)
+        del f, o, gf, sums, sums0, ws, table, table0
+    H, W, E = 721, 1440, 16
+    kw = dict(img_shape=(H, W), crop_shape=(H, W), crop_offset=(0, 0), channel_names=[str(c) for c in range(C)], grid_type="equiangular")
+    x = torch.randn(B, E, C, H, W, device=dev).bfloat16().requires_grad_(True)
+    y = torch.randn(B, C, H, W, device=dev).bfloat16()
+    mods = {"corrected": ma.CorrectedSpectralL2EnergyScoreLoss(**kw).to(dev), "spectral_l2": ma.SpectralL2EnergyScoreLoss(**kw).to(dev)}
+
+    def step(mod):
+        torch.autograd.grad(mod(x, y).sum(), x)
+
+    times = {k: [] for k in mods}
+    for _ in range(3):
+        for k, mod in mods.items():
+            times[k].append(timeit(lambda: step(mod), reps=3, warm=1))
+    for k, ts in times.items():
+        print(f"module {k:12s} 721 x 1440 C = 73 E = 16 bf16, forward + backward: {fmt(ts)}", flush=True)
+    del x, y
+    E = 4
+    f = torch.randn(B, E, C, L, M, dtype=torch.complex64, device=dev).requires_grad_(True)
+    o = torch.randn(B, C, L, M, dtype=torch.complex64, device=dev)
+
+    def broadcast():          # energy_score.py:962-1038, channel_reduction=True, no NaNs
+        fe = torch.moveaxis(f, 1, 0)
+        pp, pt = (q * fe.abs().square()).sum(-1).mean(0).sum(-1, keepdim=True), (q * o.abs().square()).sum(-1).sum(-1, keepdim=True)
+        sp = (q * (fe.unsqueeze(1) - fe.unsqueeze(0)).abs().square()).sum(-3, keepdim=True).sum(-1)
+        sk = (q * (o - fe).abs().square()).sum(-3, keepdim=True).sum(-1)
+        ms, mk = sp < 1e-6, sk < 1e-6
+        sp = torch.where(ms, 0.0, torch.where(ms, 1e-6, sp).sqrt()).sum((0, 1)) * E / (E * E * (E - 1))
+        sk = torch.where(mk, 0.0, torch.where(mk, 1e-6, sk).sqrt()).sum(0) / E
+        torch.autograd.grad((sk - 0.5 * sp * pt / (pp + 1e-6)).sum(), f)
+
+    def fused():
+        torch.autograd.grad(CorrectedEnergyScoreFn.apply(f, o, q, True, 1.0, 1.0, 1e-6, []).sum(), f)
+
+    times = {"kernels": [], "broadcast torch": []}
+    for _ in range(3):
+        times["kernels"].append(timeit(fused, reps=3, warm=1))
+        times["broadcast torch"].append(timeit(broadcast, reps=3, warm=1))
+    for k, ts in times.items():
+        print(f"coefficients E = 4, forward + backward, {k:15s}: {fmt(ts)}", flush=True)
 
 
 if __name__ == "__main__":
